@@ -17,7 +17,24 @@ tests/test_gpu_batches.py) while each batch's multi-step tail -- as long as
 its longest-lived photon's serial chain -- runs on a second HIP stream under
 the next batch's first-step queueing, binning and BVH walk (which draw no
 random numbers).  detail.step_ms is then each call's time split over its
-steps.  A short sequential run of the same steps follows, untimed for the
+steps.
+
+A plain run does what the headline figure needs and no more: set-up, warm-up,
+the timed steps, the outputs of the last timed step when --dump-outputs DIR is
+given, and the result line.  Everything else described below -- the sequential
+run, the slot-timing and counting passes, the CPU baseline, the parity check
+against the oracle, the roofline and the geometry hashes -- runs only with
+--full, after the timed steps, and leaves the headline as it is.
+
+--dump-outputs DIR writes what the last timed step's propagate returned to its
+caller as DIR/<name>.npy (float32; integer fields as float64, exact): the
+photon fields of GPUPhotons.get() for a fixed, seeded sample of the batch
+(photon_index.npy holds the sampled indices) and channel_hit_counts.npy, the
+step's hit-channel reduce.  The inputs depend on the arguments alone, so two
+builds run with the same arguments can be compared array by array.  Ranks > 0
+write <name>.rank<r>.npy.
+
+With --full, a short sequential run of the same steps follows, untimed for the
 headline, and is reported as detail.sequential (the figure a caller making one
 propagate call at a time gets).
 
@@ -33,7 +50,7 @@ SUM-reduced over the ranks (RCCL, chroma.gpu.shard) -- the only exchange the
 path has.  The timed region is bracketed by barriers and the max over ranks
 is reported; value = photons of all ranks / that time.
 
-Parity: rank 0 runs the CPU oracle (cpu_baseline leg, the only place bench.py
+Parity (--full): rank 0 runs the CPU oracle (cpu_baseline leg, the only place bench.py
 touches oracle/) on a bounded sample of its photons with the same RNG
 initialisation, as two batches in order, then propagates the SAME two batches
 on the GPU through the path the headline used (pipelined or sequential) and
@@ -45,7 +62,7 @@ photons to rank 0, which runs the oracle for them: parity.per_rank (only rank
 0 holds the oracle's host copy of the geometry).  detail.ranks carries each
 rank's setup times (geometry build / cache load, upload) and host memory.
 
-Roofline: the dominant kernel is trace_kernel, the
+Roofline (--full): the dominant kernel is trace_kernel, the
 BVH walk of every one-step launch.  It is bound by HBM/L2 latency-bandwidth on
 dependent node/triangle gathers.
     achieved = algorithmic bytes per trace launch / average trace launch time
@@ -79,6 +96,8 @@ METRIC = 'propagated photons/sec, 29k-PMT detector, 10M isotropic photons, 1/2/4
 HBM_PEAK_GBS = 8000.0
 PHOTON_SEED = 20260102
 PUBLISHED_29K = 2.5e6      # reference README, 29k PMTs, photons/s
+DUMP_PHOTONS = 500_000     # --dump-outputs: photons of the last step kept (72 B each, 36 MB + the indices)
+DUMP_SEED = 20260103       # ... chosen by this seed when the batch holds more
 
 
 def _demo_detector(**kw):
@@ -217,6 +236,60 @@ def shared_geometry(name, cache_dir, rank, dist):
         setup['geometry_s'] = round(time.time() - t1, 2)
         setup['barrier_wait_s'] = round(t1 - t0, 2)
     return det, setup
+
+
+def default_cache_dir():
+    """The node-local geometry cache: $CHROMA_BENCH_CACHE or /tmp/chroma_bench_cache,
+    the one directory the benchmark, the GPU tests and the tools share (a second
+    copy of the 29k detector would be another 16 GB of disk)."""
+    return os.environ.get('CHROMA_BENCH_CACHE') or '/tmp/chroma_bench_cache'
+
+
+# Disk one detector's cache entry takes (GB: flattened geometry, reference BVH, traversal BVH)
+CACHE_DISK_GB = {'29k': 16.0, 'demo': 6.0, 'scint': 6.0, 'tiny': 0.1, 'small': 0.1}
+
+
+def cache_disk_room(detector, cache_dir):
+    """(fits, free GB) for writing this detector's entry under cache_dir with half
+    as much again left over for everything else that writes to that disk."""
+    d = cache_dir
+    while d and not os.path.isdir(d):
+        d = os.path.dirname(d)
+    try:
+        import shutil
+        free = shutil.disk_usage(d or '/').free / 1e9
+    except OSError:
+        return True, None
+    return free >= 1.5 * CACHE_DISK_GB.get(detector, 0.0), round(free, 1)
+
+
+def prime_cache(detector='29k', cache_dir=None):
+    """Fill the geometry cache with everything a run's set-up loads for this
+    detector -- the flattened geometry, the reference BVH and the traversal BVH
+    derived from it -- on the host, without a GPU (what rank 0 of a multi-rank
+    job does for the others).  A cold build of the 29k detector is over a
+    minute of host work that a later run then does not repeat.  Returns the
+    record of what was done; refuses (reason in the record) when the host
+    memory does not hold the build, or when the entry is not there yet and the
+    disk would be left without room (a full disk fails whatever runs next)."""
+    cache_dir = cache_dir or default_cache_dir()
+    pre = preflight_host_memory(detector, 1)
+    if not pre['fits']:
+        return {'primed': False, 'reason': 'needs ~%.0f GB of host memory, %.0f GB available' % (
+            pre['need_gb'], pre['available_gb'])}
+    if not os.path.exists(os.path.join(cache_dir, 'geo', 'bench_%s' % detector)):
+        fits, free = cache_disk_room(detector, cache_dir)
+        if not fits:
+            return {'primed': False, 'reason': 'the entry takes ~%.0f GB of disk, %.1f GB free under %s' % (
+                CACHE_DISK_GB[detector], free, cache_dir)}
+    from chroma.gpu import _native, wide_bvh
+    _native.set_host_threads(usable_cpus())
+    t0 = time.time()
+    det = build_geometry(detector, cache_dir)
+    t1 = time.time()
+    source = wide_bvh.prepare(det)
+    return {'primed': True, 'cache_dir': cache_dir, 'geometry_s': round(t1 - t0, 1),
+            'wide_bvh_source': source, 'wide_bvh_s': round(time.time() - t1, 1)}
 
 
 def _native_host_threads():
@@ -438,6 +511,31 @@ def result_line(args, world, elapsed, per_step_s, total_photons, detector_info, 
     }
 
 
+def dump_sample(n):
+    """Indices of the photons --dump-outputs keeps of an n-photon batch: all of
+    them, or a fixed seeded sample of DUMP_PHOTONS (ascending)."""
+    if n <= DUMP_PHOTONS:
+        return np.arange(n, dtype=np.int64)
+    return np.sort(np.random.RandomState(DUMP_SEED).choice(n, DUMP_PHOTONS, replace=False)).astype(np.int64)
+
+
+def dump_outputs(outputs, directory, rank):
+    """Write a step's outputs (name -> array) as DIR/<name>.npy (rank 0) or
+    DIR/<name>.rank<r>.npy: floats as float32, everything else as float64
+    (exact for the 32-bit integer fields).  Returns the bytes written."""
+    os.makedirs(directory, exist_ok=True)
+    total = 0
+    for name, a in sorted(outputs.items()):
+        a = np.asarray(a)
+        a = np.ascontiguousarray(a, np.float32 if a.dtype == np.float32 else np.float64)
+        np.save(os.path.join(directory, '%s%s.npy' % (name, '' if rank == 0 else '.rank%d' % rank)), a,
+                allow_pickle=False)
+        total += a.nbytes
+    log('rank %d: outputs of the last timed step written to %s (%d arrays, %.1f MB)' % (
+        rank, directory, len(outputs), total / 1e6))
+    return total
+
+
 def _kernel_info(native):
     try:
         return native.kernel_info()
@@ -618,6 +716,18 @@ class PropagateWorkload(object):
 
     def run_sequential(self, m):
         return self.run(m, pipeline=False)
+
+    def outputs(self):
+        """What the last step of the last run() returned to its caller (--dump-outputs):
+        the photon fields of GPUPhotons.get() on the dump_sample of the batch, the
+        sampled indices, and the step's reduced hit-channel counts."""
+        ph = self.reduced['gp'].get()
+        idx = dump_sample(len(ph.pos))
+        out = {f: getattr(ph, f)[idx] for f in ('pos', 'dir', 'pol', 'wavelengths', 't', 'last_hit_triangles',
+                                                'flags', 'weights', 'evidx')}
+        out['photon_index'] = idx
+        out['channel_hit_counts'] = self.reduced['counts'].cpu().numpy()
+        return out
 
     def at_max_steps(self, nbatches):
         """Photons of each of the last call's batches that ran out of steps: their
@@ -884,6 +994,13 @@ def parse_args(argv=None):
     ap.add_argument('--nthreads-per-block', type=int, default=512)
     ap.add_argument('--max-blocks', type=int, default=1024)
     ap.add_argument('--seed', type=int, default=1)
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps: write what the last timed step returned (photon fields of a fixed '
+                         'seeded sample, hit-channel counts) as DIR/<name>.npy')
+    ap.add_argument('--full', action='store_true',
+                    help='after the timed steps also run everything beyond the headline: the sequential run, the '
+                         'slot-timing and counting passes, the CPU baseline, parity against the oracle, roofline '
+                         'and geometry hashes (the options below shape these; without --full none of them runs)')
     ap.add_argument('--cpu-budget', type=float, default=20.0, help='seconds of CPU-baseline work')
     ap.add_argument('--parity-photons', type=int, default=0,
                     help='rank 0: a fixed parity / cpu_baseline sample of this many photons (0: grown to '
@@ -907,10 +1024,16 @@ def parse_args(argv=None):
     ap.add_argument('--sequential-steps', type=int, default=20,
                     help='after the pipelined headline: this many one-call-per-step steps, timed the same way '
                          '(detail.sequential; 0: skip)')
-    ap.add_argument('--cache-dir', default=os.environ.get('CHROMA_BENCH_CACHE', '/tmp/chroma_bench_cache'))
+    ap.add_argument('--cache-dir', default=default_cache_dir(),
+                    help='node-local geometry cache ($CHROMA_BENCH_CACHE, default /tmp/chroma_bench_cache; '
+                         'build() of __graft_entry__.py prepares the default detector there)')
     args = ap.parse_args(argv)
     if args.gpus < 1:
         ap.error('--gpus must be >= 1')
+    if args.steps < 1:
+        ap.error('--steps must be >= 1 (the timed steps)')
+    if args.warmup < 0:
+        ap.error('--warmup must be >= 0')
     if args.total_photons and args.total_photons < args.gpus:
         ap.error('--total-photons must give every GPU at least one photon')
     return args
@@ -1003,9 +1126,12 @@ def run_rank(args):
     total_photons = nphotons * args.steps
     if dist is not None:
         total_photons = int(round(_allreduce(dist, float(total_photons), 'sum')))
+    if args.dump_outputs:
+        # before any later pass reuses the batches' device arrays
+        dump_outputs(wl.outputs(), args.dump_outputs, rank)
     report = wl.rank_report(stats)
     seq = None
-    if args.pipeline and args.sequential_steps > 0:
+    if args.full and args.pipeline and args.sequential_steps > 0:
         # warm-up first: a propagate call uses its own buffer context, whose first use
         # allocates it (r03's 5-step figure, 350.7 M/s, timed that allocation)
         s_el, _, _ = timed_loop(wl.run_sequential, args.sequential_steps, 2, dist, wl.sync, 1)
@@ -1022,7 +1148,7 @@ def run_rank(args):
     # slot's events reports the rest
     timing_pass = None
     tsteps = min(args.timing_steps, len(getattr(wl, 'pool', [])) or args.timing_steps)
-    if tsteps > 0:
+    if args.full and tsteps > 0:
         prev = os.environ.get('CHR_SLOT_TIMING')
         os.environ['CHR_SLOT_TIMING'] = '1'
         t_el, _, t_stats = timed_loop(wl.run, tsteps, 0, dist, wl.sync, min(wl.group, tsteps))
@@ -1038,7 +1164,7 @@ def run_rank(args):
                        'tail_ms': [t['ms'] for t in t_rep['tail']],
                        'note': 'untimed pass after the timed steps with every slot event recorded '
                                '(CHR_SLOT_TIMING=1); the timed steps record only the trace launch pairs'}
-    extra = wl.untimed_passes()
+    extra = wl.untimed_passes() if args.full else {}
 
     # oracle checks: ranks > 0 propagate a sample of their own shard on their GPU and
     # send the photons to rank 0; rank 0 runs the timed cpu_baseline alone on the host
@@ -1048,7 +1174,7 @@ def run_rank(args):
     # host copy of the geometry and every rank's sample: reported apart)
     report.update(host_memory())
     check, samples = None, None
-    if not args.no_cpu_baseline:
+    if args.full and not args.no_cpu_baseline:
         mine = None
         if rank > 0:
             mine = wl.gpu_sample(min(nphotons, args.rank_parity_photons), args.pipeline)
@@ -1114,7 +1240,9 @@ def run_rank(args):
             result['parity'] = parity
             if r0['trace_launches']:
                 result['roofline'] = roofline(args, reports, ostats)
-        result['geometry_md5_match'] = geometry_md5_check(args.detector, getattr(wl, 'det', None), detail)
+        result['geometry_md5_match'] = (geometry_md5_check(args.detector, getattr(wl, 'det', None), detail)
+                                        if args.full else None)
+        result['full'] = bool(args.full)
         print(json.dumps(result), flush=True)
         if check is not None and not result['parity']['ok']:
             log('bench.py: PARITY FAILED against the oracle (parity.ok false; parity.floats / '

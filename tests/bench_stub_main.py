@@ -65,6 +65,14 @@ class StubWorkload(object):
     def run_sequential(self, m):
         return self.run(m, pipeline=False)
 
+    def outputs(self):
+        # --dump-outputs: stand-in arrays of the types the real outputs have
+        import numpy as np
+        idx = bench.dump_sample(self.nphotons)
+        pos = np.random.RandomState(self.rank).uniform(-1.0, 1.0, (self.nphotons, 3)).astype(np.float32)
+        return {'pos': pos[idx], 'flags': np.full(len(idx), 4, np.uint32), 'photon_index': idx,
+                'channel_hit_counts': self.reduced['counts'].cpu().numpy()}
+
     def rank_report(self, stats):
         return {'rank': self.rank, 'photons_per_step': self.nphotons, 'device': 'stub', 'local_rank': self.rank,
                 'host': 'stub', 'kernel_ms': sum(s.kernel_ms for s in stats),
@@ -82,7 +90,7 @@ class StubWorkload(object):
         return {}
 
     def device_info(self):
-        return {'device': 'stub', 'kernels': []}
+        return {'device': 'stub', 'kernels': [], 'stub_calls': self.calls}
 
     def detector_info(self):
         return {'triangles': 0, 'bvh_nodes': 0, 'channels': 4}

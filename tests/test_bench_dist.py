@@ -90,15 +90,17 @@ def test_bench_world2_scaffolding(tmp_path):
         assert r[5] == 3 and r[6] == 4 and r[7] == 7 and r[8] == 3
 
 
-def _stub_bench(args, env_extra=None, timeout=120):
+def _stub_bench(args, env_extra=None, timeout=120, full=True):
     """Run tests/bench_stub_main.py (bench.py with a CPU stand-in workload) as
-    the driver would run bench.py, with a fresh node-local cache; returns
-    (returncode, parsed line or None, stderr)."""
+    the driver would run bench.py --full (full=False: a plain run), with a fresh
+    node-local cache; returns (returncode, parsed line or None, stderr)."""
     import json
     import subprocess
     import tempfile
     if '--cache-dir' not in args:
         args = list(args) + ['--cache-dir', tempfile.mkdtemp(prefix='bench_stub_cache_')]
+    if full:
+        args = list(args) + ['--full']
     env = {k: v for k, v in os.environ.items() if k not in ('WORLD_SIZE', 'RANK', 'LOCAL_RANK', 'MASTER_ADDR',
                                                             'MASTER_PORT')}
     env.update(env_extra or {})
@@ -180,6 +182,75 @@ def test_bench_total_photons_is_strong_scaling():
     assert [r['photons_per_step'] for r in line['detail']['ranks']] == [500, 501]
     assert line['value'] == pytest.approx(1001 * 2 / (line['ms_per_step'] * 2 / 1e3))
     assert line['detail']['sequential'] is None
+
+
+def test_bench_plain_run_is_lean_and_dumps_outputs(tmp_path):
+    """A plain run (no --full) times its --steps steps and nothing else: no
+    sequential, slot-timing or counting pass, no CPU baseline, parity, roofline
+    or geometry hashes; the headline fields are there.  --dump-outputs DIR
+    writes the last timed step's outputs as float32 / float64 .npy, the same
+    from run to run."""
+    dirs = [str(tmp_path / 'a'), str(tmp_path / 'b')]
+    for d in dirs:
+        rc, line, err = _stub_bench(['--gpus', '1', '--steps', '3', '--warmup', '1', '--photons', '1000',
+                                     '--detector', 'small', '--dump-outputs', d], full=False)
+        assert rc == 0, err
+        assert line['full'] is False and line['steps'] == 3 and len(line['detail']['step_ms']) == 3
+        assert line['unit'] == 'photons/s' and line['higher_is_better'] is True and line['dtype'] == 'f32'
+        assert line['value'] == pytest.approx(1000 * 3 / (line['ms_per_step'] * 3 / 1e3))
+        assert line['ms_per_step'] >= 10.0                  # the stand-in step sleeps 10 ms
+        assert line['parity'] is None and line['cpu_baseline'] is None and line['roofline'] is None
+        assert line['geometry_md5_match'] is None
+        assert line['detail']['sequential'] is None and line['detail']['slot_timing_pass'] is None
+        # the stand-in saw the warm-up (2 steps for a pipelined run) and the timed steps only
+        assert line['detail']['stub_calls'] == [[2, True], [3, True]]
+    names = sorted(os.listdir(dirs[0]))
+    assert names == ['channel_hit_counts.npy', 'flags.npy', 'photon_index.npy', 'pos.npy']
+    assert sorted(os.listdir(dirs[1])) == names
+    for n in names:
+        a, b = np.load(os.path.join(dirs[0], n)), np.load(os.path.join(dirs[1], n))
+        assert a.dtype in (np.float32, np.float64) and np.array_equal(a, b)
+    assert np.load(os.path.join(dirs[0], 'pos.npy')).dtype == np.float32
+    assert np.array_equal(np.load(os.path.join(dirs[0], 'flags.npy')), np.full(1000, 4.0))
+    assert np.array_equal(np.load(os.path.join(dirs[0], 'channel_hit_counts.npy')), [1.0, 0.0, 0.0, 0.0])
+
+
+def test_bench_dump_sample_is_fixed():
+    """--dump-outputs keeps every photon of a small batch and a fixed, seeded,
+    ascending sample of a large one (at most 64 MB of float32 / float64 in all)."""
+    sys.path.insert(0, ROOT)
+    import bench
+    assert np.array_equal(bench.dump_sample(1000), np.arange(1000))
+    a, b = bench.dump_sample(10_000_000), bench.dump_sample(10_000_000)
+    assert np.array_equal(a, b) and len(a) == bench.DUMP_PHOTONS and len(np.unique(a)) == len(a)
+    assert np.all(np.diff(a) > 0) and a[0] >= 0 and a[-1] < 10_000_000
+    # 12 float32 + 3 float64 fields per photon, the indices, the 29k detector's channel counts
+    assert bench.DUMP_PHOTONS * (12 * 4 + 3 * 8 + 8) + 29007 * 8 <= 64e6
+
+
+def test_bench_prime_cache_leaves_room_on_disk(tmp_path, monkeypatch):
+    """bench.prime_cache (what build() runs on a GPU machine) fills the cache the
+    benchmark and the GPU tests share -- one copy -- and refuses to write an entry
+    that would leave the disk with less than half the entry's size again."""
+    import collections
+    import shutil
+    sys.path.insert(0, ROOT)
+    import bench
+    monkeypatch.delenv('CHROMA_BENCH_CACHE', raising=False)
+    assert bench.default_cache_dir() == '/tmp/chroma_bench_cache'
+    monkeypatch.setenv('CHROMA_BENCH_CACHE', str(tmp_path / 'env'))
+    assert bench.default_cache_dir() == str(tmp_path / 'env')
+    monkeypatch.setenv('CHROMA_BENCH_MEMAVAILABLE_GB', '500')
+    usage = collections.namedtuple('usage', 'total used free')
+    monkeypatch.setattr(shutil, 'disk_usage', lambda p: usage(100e9, 80e9, 20e9))
+    cache = str(tmp_path / 'cache')
+    r = bench.prime_cache('29k', cache)       # 16 GB entry, 20 GB free: not written
+    assert r['primed'] is False and '20.0 GB free' in r['reason'] and not os.path.exists(cache)
+    r = bench.prime_cache('small', cache)
+    assert r['primed'] and r['wide_bvh_source'] == 'built' and r['cache_dir'] == cache
+    monkeypatch.setattr(shutil, 'disk_usage', lambda p: usage(100e9, 100e9, 0.0))
+    r = bench.prime_cache('small', cache)     # the entry is there: nothing to write
+    assert r['primed'] and r['wide_bvh_source'] == 'cache'
 
 
 def test_bench_failed_rank_fails_the_run():

@@ -13,7 +13,7 @@ tail -1 "$O/smoke.log"
 timeout -k 10 900 python -u -m pytest tests -m gpu -x -v --timeout 600 --timeout-method thread > "$O/pytest_gpu.log" 2>&1 || { tail -20 "$O/pytest_gpu.log"; exit 1; }
 tail -1 "$O/pytest_gpu.log"
 cd /tmp && export TMPDIR=/tmp CHROMA_BENCH_CACHE=/tmp/chroma_bench_cache
-timeout -k 10 600 python3 "$R/bench.py" --steps 20 --warmup 5 > "$O/bench.json" 2> "$O/bench.log" || exit $?
+timeout -k 10 600 python3 "$R/bench.py" --full --steps 20 --warmup 5 > "$O/bench.json" 2> "$O/bench.log" || exit $?
 cut -c1-200 "$O/bench.json"
 if [ "${WARM:-1}" = 1 ]; then
   timeout -k 10 300 python3 "$R/bench.py" --steps 3 --warmup 1 --no-cpu-baseline --sequential-steps 0 \

@@ -9,7 +9,7 @@ O=$R/gpurun_out/$T
 mkdir -p "$O"
 export CHROMA_BENCH_CACHE=/tmp/chroma_bench_cache
 cd /tmp && export TMPDIR=/tmp
-CHROMA_DEVICE_PROFILE=1 timeout -k 10 600 python3 "$R/bench.py" --steps 3 --warmup 2 --no-cpu-baseline --no-count \
+CHROMA_DEVICE_PROFILE=1 timeout -k 10 600 python3 "$R/bench.py" --full --steps 3 --warmup 2 --no-cpu-baseline --no-count \
     --sequential-steps 0 --timing-steps 0 "$@" > "$O/bench.json" 2> "$O/bench.log" || { tail -20 "$O/bench.log"; exit 1; }
 python3 - "$O/bench.json" <<'PY'
 import json, sys

@@ -18,5 +18,5 @@ if [ "${WITH_PROF:-1}" = 1 ]; then
   cp "$O/prof/pmc_traffic.json" "$R/profiles/latest_pmc.json" || exit $?
 fi
 cd /tmp && export TMPDIR=/tmp CHROMA_BENCH_CACHE=/tmp/chroma_bench_cache
-timeout -k 10 600 python3 "$R/bench.py" --steps 20 --warmup 5 > "$O/bench.json" 2> "$O/bench.log" || exit $?
+timeout -k 10 600 python3 "$R/bench.py" --full --steps 20 --warmup 5 > "$O/bench.json" 2> "$O/bench.log" || exit $?
 cut -c1-300 "$O/bench.json"

@@ -17,6 +17,6 @@ for c in $WANT; do grep -qw "$c" "$O/counters.txt" && HAVE="$HAVE $c"; done
 echo "counters:$HAVE"
 [ -n "$HAVE" ] || exit 1
 env "$@" timeout -s KILL 600 rocprofv3 --pmc $HAVE --output-format csv -d "$O/sq" -o run -- \
-    python3 "$R/bench.py" --no-cpu-baseline --no-count --steps 2 --warmup 1 > "$O/bench_sq.json" 2> "$O/bench_sq.log" \
+    python3 "$R/bench.py" --full --no-cpu-baseline --no-count --steps 2 --warmup 1 > "$O/bench_sq.json" 2> "$O/bench_sq.log" \
     || { tail -20 "$O/bench_sq.log"; exit 1; }
 echo "sq ok"
