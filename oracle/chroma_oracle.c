@@ -1139,13 +1139,33 @@ static void chunk_iter(int nelements, int ntpb, int maxb, int first, int *count)
     *count = left < blocks * ntpb ? left : blocks * ntpb;
 }
 
-/* GPUPhotons.propagate (photon.py:226-293), track=False, stable compaction.
- * Photon arrays are host arrays updated in place; rng states SoA. */
-EXPORT int orc_propagate(const chr_geometry_desc *d, float *pos, float *dir, float *pol, float *wavelengths,
-                         float *t, uint32_t *flags, int32_t *last_hit, float *weights, uint32_t *evidx,
-                         uint32_t nphotons_total, uint32_t true_nphotons, uint32_t ncopies,
-                         uint32_t *rng, uint32_t nslots, int ntpb, int max_blocks, int max_steps,
-                         int use_weights, int scatter_first, int omp_threads, uint64_t *stats_out) {
+static void snapshot_photon(const Photons *ph, uint32_t i, uint32_t *w) {
+    memcpy(w, ph->pos + 3 * (size_t)i, 12);
+    memcpy(w + 3, ph->dir + 3 * (size_t)i, 12);
+    memcpy(w + 6, ph->pol + 3 * (size_t)i, 12);
+    w[9] = fbits(ph->wavelengths[i]); w[10] = fbits(ph->t[i]); w[11] = ph->flags[i];
+    w[12] = (uint32_t)ph->last_hit[i]; w[13] = fbits(ph->weights[i]); w[14] = ph->evidx[i]; w[15] = 0;
+}
+
+/* GPUPhotons.propagate (photon.py:226-293), stable compaction.  Photon arrays
+ * are host arrays updated in place; rng states SoA.  track != 0 is the
+ * reference's track=True policy (photon.py:261-264): every host step is a
+ * single step whatever the live count; the queueing, chunking, compaction and
+ * scatter_first reset are the same.  With track, step_counts (max_steps + 1
+ * words) and step_ids (step_ids_cap words), when given, record the reference's
+ * step_photon_ids: entry 0 the initial queue, entry k the queue that entered
+ * host step k, back to back; *nentries_out the number of entries.  step_state
+ * (16 words per recorded id, NULL: none) records its step_photons: the
+ * photon's pos, dir, pol, wavelength, t, flags, last hit, weight, evidx when
+ * the entry is taken -- before the first step for entry 0, after host step k
+ * for entry k. */
+static int propagate_loop(const chr_geometry_desc *d, float *pos, float *dir, float *pol, float *wavelengths,
+                          float *t, uint32_t *flags, int32_t *last_hit, float *weights, uint32_t *evidx,
+                          uint32_t nphotons_total, uint32_t true_nphotons, uint32_t ncopies,
+                          uint32_t *rng, uint32_t nslots, int ntpb, int max_blocks, int max_steps,
+                          int use_weights, int scatter_first, int omp_threads, uint64_t *stats_out, int track,
+                          uint32_t *step_counts, uint32_t *step_ids, uint64_t step_ids_cap, uint32_t *nentries_out,
+                          uint32_t *step_state) {
     init_once();
     Photons ph = {pos, dir, pol, wavelengths, t, weights, flags, last_hit, evidx};
     if ((uint64_t)ntpb * (uint64_t)max_blocks > nslots) return CHR_ERR_INVALID;
@@ -1162,8 +1182,24 @@ EXPORT int orc_propagate(const chr_geometry_desc *d, float *pos, float *dir, flo
     memset(&st, 0, sizeof(st));
     int nphotons = (int)nphotons_total;
     int step = 0;
-    while (step < max_steps) {
-        int nsteps = (nphotons < ntpb * 16 * 8 || use_weights) ? max_steps - step : 1;
+    uint32_t nentries = 0;
+    uint64_t recorded = 0;
+    int record_overflow = 0;
+#define RECORD_QUEUE() do { \
+        if (track && step_counts && step_ids) { \
+            if (recorded + (uint64_t)nphotons > step_ids_cap) record_overflow = 1; \
+            else { \
+                memcpy(step_ids + recorded, qin + 1, sizeof(uint32_t) * (size_t)nphotons); \
+                if (step_state) \
+                    for (int k_ = 0; k_ < nphotons; ++k_) \
+                        snapshot_photon(&ph, qin[1 + k_], step_state + 16 * (recorded + (uint64_t)k_)); \
+                recorded += (uint64_t)nphotons; \
+                step_counts[nentries++] = (uint32_t)nphotons; \
+            } \
+        } } while (0)
+    RECORD_QUEUE();
+    while (step < max_steps && !record_overflow) {
+        int nsteps = (!track && (nphotons < ntpb * 16 * 8 || use_weights)) ? max_steps - step : 1;
         int first = 0;
         while (first < nphotons) {
             int count;
@@ -1175,6 +1211,7 @@ EXPORT int orc_propagate(const chr_geometry_desc *d, float *pos, float *dir, flo
                 if (alive[id]) qout[qout[0]++] = qin[1 + first + id];
             first += count;
         }
+        RECORD_QUEUE();
         st.host_steps++;
         step += nsteps;
         scatter_first = 0;
@@ -1191,8 +1228,34 @@ EXPORT int orc_propagate(const chr_geometry_desc *d, float *pos, float *dir, flo
         stats_out[6] = (step < max_steps) ? (uint64_t)(qin[0] - 1) : 0;
         stats_out[7] = st.traversals;
     }
+#undef RECORD_QUEUE
+    if (nentries_out) *nentries_out = nentries;
     free(qin); free(qout); free(alive);
-    return 0;
+    return record_overflow ? CHR_ERR_INVALID : 0;
+}
+
+EXPORT int orc_propagate(const chr_geometry_desc *d, float *pos, float *dir, float *pol, float *wavelengths,
+                         float *t, uint32_t *flags, int32_t *last_hit, float *weights, uint32_t *evidx,
+                         uint32_t nphotons_total, uint32_t true_nphotons, uint32_t ncopies,
+                         uint32_t *rng, uint32_t nslots, int ntpb, int max_blocks, int max_steps,
+                         int use_weights, int scatter_first, int omp_threads, uint64_t *stats_out) {
+    return propagate_loop(d, pos, dir, pol, wavelengths, t, flags, last_hit, weights, evidx, nphotons_total,
+                          true_nphotons, ncopies, rng, nslots, ntpb, max_blocks, max_steps, use_weights,
+                          scatter_first, omp_threads, stats_out, 0, NULL, NULL, 0, NULL, NULL);
+}
+
+/* orc_propagate with the track=True step policy; see propagate_loop */
+EXPORT int orc_propagate_track(const chr_geometry_desc *d, float *pos, float *dir, float *pol, float *wavelengths,
+                               float *t, uint32_t *flags, int32_t *last_hit, float *weights, uint32_t *evidx,
+                               uint32_t nphotons_total, uint32_t true_nphotons, uint32_t ncopies,
+                               uint32_t *rng, uint32_t nslots, int ntpb, int max_blocks, int max_steps,
+                               int use_weights, int scatter_first, int omp_threads, uint64_t *stats_out,
+                               uint32_t *step_counts, uint32_t *step_ids, uint64_t step_ids_cap,
+                               uint32_t *nentries_out, uint32_t *step_state) {
+    return propagate_loop(d, pos, dir, pol, wavelengths, t, flags, last_hit, weights, evidx, nphotons_total,
+                          true_nphotons, ncopies, rng, nslots, ntpb, max_blocks, max_steps, use_weights,
+                          scatter_first, omp_threads, stats_out, 1, step_counts, step_ids, step_ids_cap,
+                          nentries_out, step_state);
 }
 
 /* single-photon single-step probes for unit tests of the physics pieces */

@@ -34,6 +34,7 @@ def lib():
         l.orc_rng_uniforms.argtypes = [vp, u32, u32, i32, vp]
         l.orc_distance_to_mesh.argtypes = [vp, i32, vp, vp, vp, vp, vp]
         l.orc_propagate.argtypes = [vp] + [vp] * 9 + [u32, u32, u32, vp, u32, i32, i32, i32, i32, i32, i32, vp]
+        l.orc_propagate_track.argtypes = l.orc_propagate.argtypes + [vp, vp, u64, vp, vp]
         l.orc_fill_state.argtypes = [vp, vp, ctypes.c_int32, ctypes.c_float, vp, vp]
         l.orc_math.argtypes = [i32, i32, vp, vp, vp]
         l.orc_rayleigh.argtypes = [i32, vp, vp, vp, u32]
@@ -129,24 +130,82 @@ class HostPhotons(object):
 
 
 def propagate(packed, photons, rng_states, nslots, nthreads_per_block=256, max_blocks=1024, max_steps=10,
-              use_weights=False, scatter_first=0, ncopies=1, true_nphotons=None, threads=None):
+              use_weights=False, scatter_first=0, ncopies=1, true_nphotons=None, threads=None, track=False):
     """GPUPhotons.propagate semantics on the host; photons (HostPhotons) and
-    rng_states are updated in place.  Returns the oracle's stats dict."""
+    rng_states are updated in place.  Returns the oracle's stats dict.
+    track=True: the reference's track=True step policy (every host step a
+    single step, photon.py:261-264); the dict then also carries 'step_ids', the
+    reference's step_photon_ids (entry 0 the initial queue, entry k the queue
+    that entered host step k), and 'step_photons', its step_photons: one
+    HostPhotons per entry, the photons of step_ids[k] in that order as they
+    were when the entry was taken (entry 0 before the first step, entry k
+    after host step k)."""
     n = len(photons)
     true_n = n // ncopies if true_nphotons is None else true_nphotons
     stats = np.zeros(8, dtype=np.uint64)
     threads = threads or os.cpu_count() or 1
     desc = packed.desc()
-    rc = lib().orc_propagate(ctypes.addressof(desc), _p(photons.pos), _p(photons.dir), _p(photons.pol),
-                             _p(photons.wavelengths), _p(photons.t), _p(photons.flags),
-                             _p(photons.last_hit_triangles), _p(photons.weights), _p(photons.evidx),
-                             n, true_n, ncopies, _p(rng_states), nslots, nthreads_per_block, max_blocks,
-                             max_steps, int(bool(use_weights)), int(scatter_first), threads, _p(stats))
+    args = (ctypes.addressof(desc), _p(photons.pos), _p(photons.dir), _p(photons.pol),
+            _p(photons.wavelengths), _p(photons.t), _p(photons.flags),
+            _p(photons.last_hit_triangles), _p(photons.weights), _p(photons.evidx),
+            n, true_n, ncopies, _p(rng_states), nslots, nthreads_per_block, max_blocks,
+            max_steps, int(bool(use_weights)), int(scatter_first), threads, _p(stats))
+    if track:
+        counts = np.zeros(max(max_steps, 0) + 1, dtype=np.uint32)
+        ids = np.zeros(max(1, (max(max_steps, 0) + 1) * n), dtype=np.uint32)
+        nentries = np.zeros(1, dtype=np.uint32)
+        state = np.zeros((len(ids), 16), dtype=np.uint32)
+        rc = lib().orc_propagate_track(*(args + (_p(counts), _p(ids), len(ids), _p(nentries), _p(state))))
+    else:
+        rc = lib().orc_propagate(*args)
     if rc != 0:
         raise RuntimeError('orc_propagate failed with status %d' % rc)
     keys = ('nodes_visited', 'tris_tested', 'max_depth', 'overflows', 'host_steps', 'launches', 'final_alive',
             'traversals')
-    return dict(zip(keys, (int(x) for x in stats[:8])))
+    out = dict(zip(keys, (int(x) for x in stats[:8])))
+    if track:
+        bounds = np.concatenate([[0], np.cumsum(counts[:int(nentries[0])].astype(np.int64))])
+        out['step_ids'] = [ids[a:b].copy() for a, b in zip(bounds[:-1], bounds[1:])]
+        out['step_photons'] = [_unpack_state(state[a:b]) for a, b in zip(bounds[:-1], bounds[1:])]
+    return out
+
+
+def _unpack_state(words):
+    """HostPhotons from orc_propagate_track's 16-word photon records."""
+    host = HostPhotons.__new__(HostPhotons)
+    f32 = words.view(np.float32)
+    host.pos, host.dir, host.pol = (np.ascontiguousarray(f32[:, k:k + 3]) for k in (0, 3, 6))
+    host.wavelengths, host.t, host.weights = (np.ascontiguousarray(f32[:, k]) for k in (9, 10, 13))
+    host.flags = np.ascontiguousarray(words[:, 11])
+    host.last_hit_triangles = np.ascontiguousarray(words[:, 12]).view(np.int32)
+    host.evidx = np.ascontiguousarray(words[:, 14])
+    return host
+
+
+def _replicated(photons, ncopies):
+    host = HostPhotons(photons)
+    if ncopies > 1:
+        for f in host.FIELDS:
+            setattr(host, f, np.concatenate([getattr(host, f)] * ncopies))
+    return host
+
+
+def propagate_tracked(packed, photons, seed, nslots, nthreads_per_block=256, max_blocks=1024, max_steps=10,
+                      use_weights=False, scatter_first=0, ncopies=1, threads=None):
+    """What GPUPhotons.propagate(track=True) returns (photon.py:252-293), on the
+    host: (step_photon_ids, step_photons, final photons, final rng states)
+    of a tracked run from copies of `photons` (replicated ncopies times) and a
+    fresh rng_init(nslots, seed).  step_photons[k] is a HostPhotons of the
+    photons step_photon_ids[k] names, in that order: entry 0 their initial
+    state, entry k >= 1 their state after k steps (tests/test_oracle_tracked.py
+    pins the entries against fresh k-step runs)."""
+    host = _replicated(photons, ncopies)
+    st = rng_init(nslots, seed=seed)
+    # one thread team per chunk launch and step: a small one serves the small batches tracking is tested at
+    threads = threads or min(os.cpu_count() or 1, 8)
+    stats = propagate(packed, host, st, nslots, nthreads_per_block, max_blocks, max_steps, use_weights=use_weights,
+                      scatter_first=scatter_first, ncopies=ncopies, threads=threads, track=True)
+    return stats['step_ids'], stats['step_photons'], host, st
 
 
 class Watch(object):
