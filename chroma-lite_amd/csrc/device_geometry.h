@@ -69,6 +69,7 @@ struct DevGeom {
     uint32_t nwnodes, nwtri;
     uint32_t wstride;                // uint4 per node slot: 8 (each 96-byte node padded to one 128-byte line)
     float ox, oy, oz, scale;         // world_origin, world_scale
+    float wbound;                    // slab_world_bound of them: no wide node's plane lies beyond (slab_plane.h)
     uint32_t nnodes, ntriangles, nwireplanes;
     uint32_t wl_n;
     float wl_start, wl_step;

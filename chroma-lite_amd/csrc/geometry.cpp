@@ -16,6 +16,7 @@
 
 #include "../../include/chroma_amd.h"
 #include "common.h"
+#include "slab_plane.h"
 #include "wide_bvh.h"
 #include "device_geometry.h"
 
@@ -299,6 +300,7 @@ static int geometry_create(const chr_geometry_desc *d, const chr_wide_bvh_desc *
         chr::DevGeom &dg = g->dev;
         dg.ox = d->world_origin[0]; dg.oy = d->world_origin[1]; dg.oz = d->world_origin[2];
         dg.scale = d->world_scale;
+        dg.wbound = chr::slab_world_bound(dg.ox, dg.oy, dg.oz, dg.scale);
         dg.nnodes = d->nnodes; dg.ntriangles = d->ntriangles; dg.nwireplanes = d->nwireplanes;
         dg.wl_n = d->wavelength_n; dg.wl_start = d->wavelength_start; dg.wl_step = d->wavelength_step;
         dg.t_n = d->time_n; dg.t_start = d->time_start; dg.t_step = d->time_step;

@@ -35,6 +35,7 @@
 #include "device_geometry.h"
 #include "device_math.h"
 #include "sampling.h"
+#include "slab_plane.h"
 #include "wide_bvh.h"
 
 namespace chr {
@@ -363,18 +364,28 @@ __device__ __forceinline__ F2 pk_fma(F2 a, F2 b, F2 c) { return __builtin_elemen
 // reference's skip of the flat axis (RaySlab::flat).
 struct RaySlab {
     float inx, iny, inz;        // multipliers (inv, or 2^100 on a flat axis)
-    float onx, ony, onz;        // near offsets (noid, or -o * 2^100)
+    float onx, ony, onz;        // near offsets (noid, or -o * 2^100): exact, the leaf boxes' and the tail's
     float ofx, ofy, ofz;        // far offsets (same)
+    // The wide nodes' one-FMA planes (expand_node; slab_plane.h has the proof): the
+    // offsets moved outward by the pad eps = (|mult| W + |offset|) 2^-21, so that a
+    // child the two-FMA test enters is entered; on a wild axis (eps = +inf) -inf / +inf
+    // or NaN, which the max/min chains skip: the axis never culls.
+    float pnx, pny, pnz;        // padded near offsets
+    float pfx, pfy, pfz;        // padded far offsets
     bool negx, negy, negz;      // inv < 0: the near plane is the box's hi face
     uint32_t flat;              // bit k: axis k flat (skipped by intersect_box_slab, as the reference does)
 };
-__device__ __forceinline__ RaySlab make_slab(V3 o, V3 noid, V3 inv) {
+// W: slab_world_bound of the geometry (DevGeom::wbound)
+__device__ __forceinline__ RaySlab make_slab(V3 o, V3 noid, V3 inv, float W) {
     RaySlab r;
-    constexpr float BIG = 1.2676506e30f;   // 2^100
-    const bool fx = chr_isfinite(inv.x), fy = chr_isfinite(inv.y), fz = chr_isfinite(inv.z);
-    r.inx = fx ? inv.x : BIG; r.onx = fx ? noid.x : -(o.x * BIG); r.ofx = r.onx;
-    r.iny = fy ? inv.y : BIG; r.ony = fy ? noid.y : -(o.y * BIG); r.ofy = r.ony;
-    r.inz = fz ? inv.z : BIG; r.onz = fz ? noid.z : -(o.z * BIG); r.ofz = r.onz;
+    const bool fx = slab_finite(inv.x), fy = slab_finite(inv.y), fz = slab_finite(inv.z);
+    r.inx = slab_mult(inv.x); r.onx = slab_off(o.x, noid.x, inv.x); r.ofx = r.onx;
+    r.iny = slab_mult(inv.y); r.ony = slab_off(o.y, noid.y, inv.y); r.ofy = r.ony;
+    r.inz = slab_mult(inv.z); r.onz = slab_off(o.z, noid.z, inv.z); r.ofz = r.onz;
+    const float ex = slab_pad(r.inx, r.onx, W), ey = slab_pad(r.iny, r.ony, W), ez = slab_pad(r.inz, r.onz, W);
+    r.pnx = slab_near_off(r.onx, ex); r.pfx = slab_far_off(r.onx, ex);
+    r.pny = slab_near_off(r.ony, ey); r.pfy = slab_far_off(r.ony, ey);
+    r.pnz = slab_near_off(r.onz, ez); r.pfz = slab_far_off(r.onz, ez);
     r.negx = fx && inv.x < 0.0f; r.negy = fy && inv.y < 0.0f; r.negz = fz && inv.z < 0.0f;
     r.flat = (fx ? 0u : 1u) | (fy ? 0u : 2u) | (fz ? 0u : 4u);
     return r;
@@ -495,21 +506,27 @@ __device__ __forceinline__ uint32_t expand_node(const uint4 h, const uint4 a1, c
     const uint32_t fz0 = r.negz ? a2.x : a3.z, fz1 = r.negz ? a2.y : a3.w;
     float tk[8];
     uint32_t inner = 0, leaf = 0;
-    // two children per packed FMA (v_pk_fma_f32: each half a fused fmaf, so the
-    // plane distances are bit-identical to the scalar form above)
-    const F2 sx2 = f2(sx, sx), sy2 = f2(sy, sy), sz2 = f2(sz, sz);
-    const F2 ox2 = f2(org.x, org.x), oy2 = f2(org.y, org.y), oz2 = f2(org.z, org.z);
-    const F2 ix2 = f2(r.inx, r.inx), iy2 = f2(r.iny, r.iny), iz2 = f2(r.inz, r.inz);
-    const F2 nx2 = f2(r.onx, r.onx), ny2 = f2(r.ony, r.ony), nz2 = f2(r.onz, r.onz);
-    const F2 fx2 = f2(r.ofx, r.ofx), fy2 = f2(r.ofy, r.ofy), fz2 = f2(r.ofz, r.ofz);
+    // One FMA per plane (slab_plane.h): t = q S + O' with S = 2^e * mult and
+    // O' = fmaf(origin, mult, padded offset) formed once per node, axis and side, two
+    // children per packed FMA (v_pk_fma_f32: each half a fused fmaf, slab_t1).  The
+    // pad makes every near distance <= and every far distance >= the two-FMA form's
+    // (decode the plane as the builder checked it, then the reference's fmaf), so
+    // the children entered are a superset; the leaf acceptance stays exact.
+    const float Sx = slab_scale(sx, r.inx), Sy = slab_scale(sy, r.iny), Sz = slab_scale(sz, r.inz);
+    const float Onx = slab_origin(org.x, r.inx, r.pnx), Ofx = slab_origin(org.x, r.inx, r.pfx);
+    const float Ony = slab_origin(org.y, r.iny, r.pny), Ofy = slab_origin(org.y, r.iny, r.pfy);
+    const float Onz = slab_origin(org.z, r.inz, r.pnz), Ofz = slab_origin(org.z, r.inz, r.pfz);
+    const F2 sx2 = f2(Sx, Sx), sy2 = f2(Sy, Sy), sz2 = f2(Sz, Sz);
+    const F2 nx2 = f2(Onx, Onx), ny2 = f2(Ony, Ony), nz2 = f2(Onz, Onz);
+    const F2 fx2 = f2(Ofx, Ofx), fy2 = f2(Ofy, Ofy), fz2 = f2(Ofz, Ofz);
 #pragma unroll
     for (int k = 0; k < 8; k += 2) {
-        const F2 tnx = pk_fma(pk_fma(f2(byte_f(nx0, nx1, k), byte_f(nx0, nx1, k + 1)), sx2, ox2), ix2, nx2);
-        const F2 tfx = pk_fma(pk_fma(f2(byte_f(fx0, fx1, k), byte_f(fx0, fx1, k + 1)), sx2, ox2), ix2, fx2);
-        const F2 tny = pk_fma(pk_fma(f2(byte_f(ny0, ny1, k), byte_f(ny0, ny1, k + 1)), sy2, oy2), iy2, ny2);
-        const F2 tfy = pk_fma(pk_fma(f2(byte_f(fy0, fy1, k), byte_f(fy0, fy1, k + 1)), sy2, oy2), iy2, fy2);
-        const F2 tnz = pk_fma(pk_fma(f2(byte_f(nz0, nz1, k), byte_f(nz0, nz1, k + 1)), sz2, oz2), iz2, nz2);
-        const F2 tfz = pk_fma(pk_fma(f2(byte_f(fz0, fz1, k), byte_f(fz0, fz1, k + 1)), sz2, oz2), iz2, fz2);
+        const F2 tnx = pk_fma(f2(byte_f(nx0, nx1, k), byte_f(nx0, nx1, k + 1)), sx2, nx2);
+        const F2 tfx = pk_fma(f2(byte_f(fx0, fx1, k), byte_f(fx0, fx1, k + 1)), sx2, fx2);
+        const F2 tny = pk_fma(f2(byte_f(ny0, ny1, k), byte_f(ny0, ny1, k + 1)), sy2, ny2);
+        const F2 tfy = pk_fma(f2(byte_f(fy0, fy1, k), byte_f(fy0, fy1, k + 1)), sy2, fy2);
+        const F2 tnz = pk_fma(f2(byte_f(nz0, nz1, k), byte_f(nz0, nz1, k + 1)), sz2, nz2);
+        const F2 tfz = pk_fma(f2(byte_f(fz0, fz1, k), byte_f(fz0, fz1, k + 1)), sz2, fz2);
 #pragma unroll
         for (int h = 0; h < 2; ++h) {
             const int c = k + h;
@@ -721,7 +738,7 @@ __device__ int intersect_wide_sched(const DevGeom &g, V3 o, V3 d, float &min_dis
     if constexpr (COUNT) cnt.walks++;
     const V3 noid = v3(-o.x / d.x, -o.y / d.y, -o.z / d.z);
     const V3 inv = v3(1.0f / d.x, 1.0f / d.y, 1.0f / d.z);
-    const RaySlab slab = make_slab(o, noid, inv);
+    const RaySlab slab = make_slab(o, noid, inv, g.wbound);
     float best = __builtin_inff(), best_bd = __builtin_inff(), cut = __builtin_inff();
     uint32_t best_rank = 0xFFFFFFFFu;
     int best_id = -1;
@@ -827,7 +844,7 @@ __device__ int intersect_wide_spec(const DevGeom &g, V3 o, V3 d, float &min_dist
     if constexpr (COUNT) cnt.walks++;
     const V3 noid = v3(-o.x / d.x, -o.y / d.y, -o.z / d.z);
     const V3 inv = v3(1.0f / d.x, 1.0f / d.y, 1.0f / d.z);
-    const RaySlab slab = make_slab(o, noid, inv);
+    const RaySlab slab = make_slab(o, noid, inv, g.wbound);
     float best = __builtin_inff(), best_bd = __builtin_inff(), cut = __builtin_inff();
     uint32_t best_rank = 0xFFFFFFFFu;
     int best_id = -1;
@@ -2079,7 +2096,7 @@ __device__ __forceinline__ int walk_segment(const DevGeom &g, bool act, V3 o, V3
     const unsigned long long below = (1ull << lane) - 1ull;
     const V3 noid = v3(-o.x / d.x, -o.y / d.y, -o.z / d.z);
     const V3 inv = v3(1.0f / d.x, 1.0f / d.y, 1.0f / d.z);
-    const RaySlab r = make_slab(o, noid, inv);
+    const RaySlab r = make_slab(o, noid, inv, g.wbound);
     // cursor 0 starts at the root (UP: at start, walk_lone<true>'s climb; per segment)
     uint32_t cur = (act && L < 8u) ? (UP ? start : 0u) : INVALID;
     uint32_t chainw = INVALID;                        // UP: ancestor word k of the cursor's node (lane k)
@@ -2393,7 +2410,7 @@ __device__ __forceinline__ int walk_lone(const DevGeom &g, V3 o, V3 d, uint32_t 
     const unsigned long long below = (1ull << lane) - 1ull;
     const V3 noid = v3(-o.x / d.x, -o.y / d.y, -o.z / d.z);
     const V3 inv = v3(1.0f / d.x, 1.0f / d.y, 1.0f / d.z);
-    const RaySlab r = make_slab(o, noid, inv);
+    const RaySlab r = make_slab(o, noid, inv, g.wbound);
     uint32_t cur = lane < 8u ? (UP ? start : 0u) : INVALID;   // cursor 0 starts at the root (UP: at start)
     // UP with start's chain already read (have_pre, the tail's prefetch): cursor c > 0
     // starts at the ancestor word pre_cur (start's c-th ancestor, lane-wise; INVALID:
@@ -2707,7 +2724,7 @@ __device__ __forceinline__ int walk_pair_walker(const DevGeom &g, const TopNodes
     const unsigned long long below = (1ull << lane) - 1ull;
     const V3 noid = v3(-o.x / d.x, -o.y / d.y, -o.z / d.z);
     const V3 inv = v3(1.0f / d.x, 1.0f / d.y, 1.0f / d.z);
-    const RaySlab r = make_slab(o, noid, inv);
+    const RaySlab r = make_slab(o, noid, inv, g.wbound);
     uint32_t cur = lane < 8u ? 0u : INVALID;
     float cur_t = 0.0f;
     int sp = 0;
@@ -3508,7 +3525,7 @@ __global__ __launch_bounds__(BLOCK, MINW) void trace_kernel(const DevGeom *__res
     const uint32_t total = n;       // work items: the queued rays
     uint32_t nflat_rays = 0;        // flat rays walked by this work-item (flat-axis slab test; diagnostic)
     V3 o = v3(0.0f, 0.0f, 0.0f), d = v3(0.0f, 0.0f, 1.0f);
-    RaySlab slab = make_slab(o, o, d);
+    RaySlab slab = make_slab(o, o, d, g.wbound);
     float best = 0.0f, best_bd = 0.0f, cut = 0.0f;   // best hit, its leaf box's entry, the culling threshold
     uint32_t best_rank = 0, last = 0, node = 0;
     int best_id = -1, sp = 0;
@@ -3593,7 +3610,7 @@ __global__ __launch_bounds__(BLOCK, MINW) void trace_kernel(const DevGeom *__res
                         }
                     }
                     if (start) {
-                        slab = make_slab(o, v3(-o.x / d.x, -o.y / d.y, -o.z / d.z), v3(1.0f / d.x, 1.0f / d.y, 1.0f / d.z));
+                        slab = make_slab(o, v3(-o.x / d.x, -o.y / d.y, -o.z / d.z), v3(1.0f / d.x, 1.0f / d.y, 1.0f / d.z), g.wbound);
                         best_id = -1;
                         sp = 0;
                         walk_done = false;
@@ -3658,6 +3675,11 @@ __global__ __launch_bounds__(BLOCK, MINW) void trace_kernel(const DevGeom *__res
                 const uint4 *np = g.wnodes + (size_t)g.wstride * node;
                 h = gld(np); a1 = gld(np + 1); a2 = gld(np + 2); a3 = gld(np + 3); a4 = gld(np + 4); a5 = gld(np + 5);
             }
+            // the six loads of the node's line issue back to back: without the barrier the
+            // scheduler puts the per-node scale (first use of h) before the last load,
+            // which then waits for h to arrive before it is issued (one more latency per
+            // node step: trace 13.27 -> 13.53 ms per step on the 29k bench)
+            __builtin_amdgcn_sched_barrier(0);
 #ifdef CHR_DEVICE_PROFILE
             pf.call(P_NODE);
             for (int k = 0; k < 8; ++k)

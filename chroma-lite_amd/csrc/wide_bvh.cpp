@@ -34,6 +34,7 @@
 
 #include "../../include/chroma_amd.h"
 #include "common.h"
+#include "slab_plane.h"
 #include "wide_bvh.h"
 
 namespace chr {
@@ -420,9 +421,15 @@ int wide_validate(const chr_geometry_desc *d, const chr_wide_bvh_desc *w, WideCh
     // level's children after the level), so one forward pass gives every node's depth
     std::vector<uint16_t> depth(nn, 0);
     uint32_t maxd = 0;
+    // every plane within the bound the walk's padded one-FMA slab test is proved for
+    // (slab_plane.h; DevGeom::wbound is the same value)
+    const float wbound = slab_world_bound(d->world_origin[0], d->world_origin[1], d->world_origin[2], d->world_scale);
     for (uint32_t i = 0; i < nn; ++i) {
         const WideNode &W = N[i];
         if (W.nchild > 8) return chr::fail(CHR_ERR_INVALID, "wide BVH: node %u has %u children", i, W.nchild);
+        for (int a = 0; a < 3; ++a)
+            if (W.exp[a] == 0xFFu || !slab_planes_within(W.origin[a], pow2f((int)W.exp[a] - 127), wbound))
+                return chr::fail(CHR_ERR_INVALID, "wide BVH: node %u has a plane outside the world bound %g", i, (double)wbound);
         for (int k = 0; k < 8; ++k) {
             const uint8_t kind = W.kind[k];
             if (kind == 0) continue;
