@@ -1585,6 +1585,9 @@ struct PropagateArgs {
     // zeroed counter the photon groups take queue positions from, for queues no longer than
     // the slot count (each position then its own RNG slot, loaded and stored per photon)
     uint32_t *work;
+    // shade_kernel, live records (nullptr: the photon arrays): the slot's record buffer, one
+    // record per queue position
+    uint4 *live;
 };
 // modes of a device-driven step slot (step_head_kernel)
 constexpr uint32_t STEP_IDLE = 0, STEP_ONE = 1, STEP_TAIL = 2;
@@ -1845,6 +1848,51 @@ __device__ __forceinline__ void fetch_queued(const PropagateArgs &a, uint32_t q,
     f.last_hit = a.last_hit[f.pid];
     f.hit = a.hits[q];
 }
+// Live record of one queue position (device-driven one-step slots): the whole state of a
+// photon that is still alive, 16 words -- photon id, history, pos, dir as the step left it
+// (not normalised: the next step normalises it as it does the array's), pol, wavelength,
+// time, weight, last hit, one spare word.  A survivor's state moves from step to step in
+// these records, one aligned 64-byte line per queue position, and reaches the photon arrays
+// when the photon dies (shade_kernel) or when something else reads the arrays next
+// (scatter_queue_kernel's flush) -- not as eight partly used lines per step by photon id.
+constexpr uint32_t LIVE_QUADS = 4;   // uint4 per record
+__device__ __forceinline__ void unpack_live(uint4 r0, uint4 r1, uint4 r2, uint4 r3, QueuedPhoton &f) {
+    f.pid = r0.x;
+    f.history = r0.y;
+    f.pos = v3(__uint_as_float(r0.z), __uint_as_float(r0.w), __uint_as_float(r1.x));
+    f.dir = v3(__uint_as_float(r1.y), __uint_as_float(r1.z), __uint_as_float(r1.w));
+    f.pol = v3(__uint_as_float(r2.x), __uint_as_float(r2.y), __uint_as_float(r2.z));
+    f.wavelength = __uint_as_float(r2.w);
+    f.time = __uint_as_float(r3.x);
+    f.weight = __uint_as_float(r3.y);
+    f.last_hit = (int)r3.z;
+}
+// the record at queue position q and that position's walk result: no load depends on another
+__device__ __forceinline__ void fetch_live(const PropagateArgs &a, uint32_t q, QueuedPhoton &f) {
+    const uint4 *r = a.live + LIVE_QUADS * (size_t)q;
+    unpack_live(r[0], r[1], r[2], r[3], f);
+    f.hit = a.hits[q];
+}
+__device__ __forceinline__ void store_live(uint4 *live, uint32_t q, uint32_t pid, const Photon &p) {
+    uint4 *r = live + LIVE_QUADS * (size_t)q;
+    r[0] = make_uint4(pid, p.history, __float_as_uint(p.pos.x), __float_as_uint(p.pos.y));
+    r[1] = make_uint4(__float_as_uint(p.pos.z), __float_as_uint(p.dir.x), __float_as_uint(p.dir.y),
+                      __float_as_uint(p.dir.z));
+    r[2] = make_uint4(__float_as_uint(p.pol.x), __float_as_uint(p.pol.y), __float_as_uint(p.pol.z),
+                      __float_as_uint(p.wavelength));
+    r[3] = make_uint4(__float_as_uint(p.time), __float_as_uint(p.weight), (uint32_t)p.last_hit, 0u);
+}
+// a photon's state written to the photon arrays (propagate.cu:343-353)
+__device__ __forceinline__ void store_photon(const PropagateArgs &a, uint32_t pid, const Photon &p) {
+    store3(a.pos, pid, p.pos);
+    store3(a.dir, pid, p.dir);
+    store3(a.pol, pid, p.pol);
+    a.wl[pid] = p.wavelength;
+    a.t[pid] = p.time;
+    a.flags[pid] = p.history;
+    a.last_hit[pid] = p.last_hit;
+    a.weights[pid] = p.weight;
+}
 // The queue entry of the photon two positions ahead is loaded one iteration
 // early, so the next photon's state loads go out without first waiting for its
 // queue entry (a dependent round trip per photon otherwise; r04 ab5: 487.8-488.2 ->
@@ -1860,7 +1908,13 @@ __device__ __forceinline__ void fetch_queued(const PropagateArgs &a, uint32_t q,
 // peeled, so every path into the loop has the write-back behind the prefetch: the
 // prefetch is waited for at the physics' join, before the stores, and nothing waits
 // for the stores.
-template <int MINW, bool WIRES = true>
+// LIVE (live records: the device-driven one-step slots after a propagate's first, whose
+// scatter made the records): the photon's record is read at its queue position -- one
+// aligned 64-byte load, the photon id inside it, so no queue entry is read and nothing is
+// loaded two ahead -- and written in place by the same thread when the photon stays alive;
+// a photon that ends the step dead goes to the arrays as ever.  The waits are as above: the
+// next position's record is waited for before the write-back and nothing waits for the stores.
+template <int MINW, bool WIRES = true, bool LIVE = false>
 __global__ __launch_bounds__(BLOCK, MINW) void shade_kernel(const DevGeom *__restrict__ gdev, PropagateArgs a,
                                                             uint32_t cap) {
     if (a.mode && *a.mode != a.want) return;
@@ -1876,13 +1930,22 @@ __global__ __launch_bounds__(BLOCK, MINW) void shade_kernel(const DevGeom *__res
     pf.start(P_OTHER);
     auto clampq = [n](uint32_t q) { return q < n ? q : n - 1u; };
     QueuedPhoton nx;
-    fetch_queued(a, clampq(slot), nx);
-    uint32_t pid2 = a.input_queue[clampq(slot + cap)];   // queue entry of position pos + cap
+    uint32_t pid2 = 0u;
+    if constexpr (LIVE) {
+        fetch_live(a, clampq(slot), nx);
+    } else {
+        fetch_queued(a, clampq(slot), nx);
+        pid2 = a.input_queue[clampq(slot + cap)];   // queue entry of position pos + cap
+    }
     uint32_t pos = slot;
     auto body = [&](uint32_t qb) __attribute__((always_inline)) {
         const QueuedPhoton cur = nx;
-        fetch_queued<true>(a, clampq(pos + cap), nx, pid2);
-        pid2 = a.input_queue[clampq(pos + 2 * cap)];
+        if constexpr (LIVE) {
+            fetch_live(a, clampq(pos + cap), nx);
+        } else {
+            fetch_queued<true>(a, clampq(pos + cap), nx, pid2);
+            pid2 = a.input_queue[clampq(pos + 2 * cap)];
+        }
         bool alive = false;
         const bool valid = pos < n && !(cur.history & DEAD_MASK);
         Photon p;
@@ -1926,18 +1989,15 @@ __global__ __launch_bounds__(BLOCK, MINW) void shade_kernel(const DevGeom *__res
         // before the write-back (see above)
         asm volatile("" ::"v"(nx.pid), "v"(nx.history), "v"(nx.pos.x), "v"(nx.pos.y), "v"(nx.pos.z), "v"(nx.dir.x),
                      "v"(nx.dir.y), "v"(nx.dir.z), "v"(nx.pol.x), "v"(nx.pol.y), "v"(nx.pol.z));
-        asm volatile("" ::"v"(nx.wavelength), "v"(nx.time), "v"(nx.weight), "v"(nx.last_hit), "v"(nx.hit.x),
-                     "v"(nx.hit.y), "v"(pid2));
+        if constexpr (LIVE)
+            asm volatile("" ::"v"(nx.wavelength), "v"(nx.time), "v"(nx.weight), "v"(nx.last_hit), "v"(nx.hit.x),
+                         "v"(nx.hit.y));
+        else
+            asm volatile("" ::"v"(nx.wavelength), "v"(nx.time), "v"(nx.weight), "v"(nx.last_hit), "v"(nx.hit.x),
+                         "v"(nx.hit.y), "v"(pid2));
         if (valid) {
-            const uint32_t pid = cur.pid;
-            store3(a.pos, pid, p.pos);
-            store3(a.dir, pid, p.dir);
-            store3(a.pol, pid, p.pol);
-            a.wl[pid] = p.wavelength;
-            a.t[pid] = p.time;
-            a.flags[pid] = p.history;
-            a.last_hit[pid] = p.last_hit;
-            a.weights[pid] = p.weight;
+            if (!LIVE || !alive) store_photon(a, cur.pid, p);
+            else store_live(a.live, pos, cur.pid, p);   // in place: this thread's position
         }
         const unsigned long long mask = __ballot(alive);
         if ((slot & 63u) == 0) a.alive_masks[qb >> 6] = mask;
@@ -3919,15 +3979,70 @@ struct RayEnrol {
     uint4 *rays;
     const int32_t *last_hit;
 };
+// Survivors of a one-step slot of a propagate that carries live records (LiveCarry; out ==
+// nullptr: off).  The survivor's record is read at its queue position from the slot's
+// buffer -- no photon array is; in the propagate's first slot (in == nullptr), whose shade
+// read and wrote the arrays, it is put together from the arrays instead, a gather as
+// RayEnrol's with the other five fields -- and
+//  - the next slot is another one-step slot (*next_mode, written by the head folded into
+//    this slot's scan): the record goes to the survivor's position in the other buffer
+//    and the next walk's ray record is built from it, with put_photon_ray's operations;
+//  - anything else comes next (the tail, an empty queue, a finished propagate, no next
+//    slot at max_steps): the record is flushed to the photon arrays, which whoever reads
+//    them next -- the tail kernel, the caller, a resumed propagate -- finds as the array
+//    path leaves them (the first slot's are current already), and no ray record is built.
+struct LiveCarry {
+    const uint4 *in;
+    uint4 *out;
+    const uint32_t *next_mode;   // nullptr: no next slot
+    PropagateArgs ph;            // the photon arrays (first slot's gather, flush)
+};
 __global__ __launch_bounds__(BLOCK) void scatter_queue_kernel(const unsigned long long *masks, const uint32_t *word_offsets,
                                                                const uint32_t *block_prefix, const uint32_t *base,
                                                                const uint32_t *in_queue, int32_t first, int32_t n,
                                                                uint32_t *out_queue, RayEnrol fe, const uint32_t *dev_n,
-                                                               const uint32_t *mode, uint32_t skip) {
+                                                               const uint32_t *mode, uint32_t skip, LiveCarry lc) {
     // skip: a second mode that runs nothing here (a tail run on its own stream
     // by chr_propagate_batches leaves no queue behind)
     if (mode && (*mode == STEP_IDLE || *mode == skip)) return;
     if (dev_n) n = (int32_t)(*dev_n - 1u);
+    if (lc.out && mode && *mode == STEP_ONE) {   // (a tail slot's survivors: the arrays, below)
+        const bool forward = lc.next_mode && *lc.next_mode == STEP_ONE;
+        const PropagateArgs &a = lc.ph;
+        for (int id = blockIdx.x * BLOCK + threadIdx.x; id < n; id += gridDim.x * BLOCK) {
+            const unsigned long long m = masks[id >> 6];
+            const int lane = id & 63;
+            if (!((m >> lane) & 1ull)) continue;
+            const uint32_t rank = __popcll(m & ((1ull << lane) - 1ull));
+            const uint32_t o = base[0] + word_offset(word_offsets, block_prefix, (uint32_t)id >> 6) + rank;
+            Photon p;
+            uint32_t pid;
+            if (lc.in) {
+                const uint4 *r = lc.in + LIVE_QUADS * (size_t)id;
+                QueuedPhoton f;
+                unpack_live(r[0], r[1], r[2], r[3], f);
+                pid = f.pid;
+                p.history = f.history; p.pos = f.pos; p.dir = f.dir; p.pol = f.pol;
+                p.wavelength = f.wavelength; p.time = f.time; p.last_hit = f.last_hit; p.weight = f.weight;
+            } else {
+                pid = in_queue[first + id];
+                if (forward) {
+                    p.history = a.flags[pid] & 0xFFFFu;
+                    p.pos = load3(a.pos, pid); p.dir = load3(a.dir, pid); p.pol = load3(a.pol, pid);
+                    p.wavelength = a.wl[pid]; p.time = a.t[pid]; p.last_hit = a.last_hit[pid]; p.weight = a.weights[pid];
+                }
+            }
+            out_queue[o] = pid;
+            if (forward) {
+                store_live(lc.out, o - 1u, pid, p);
+                const V3 d = p.dir / norm(p.dir);
+                put_ray(fe.rays, o - 1u, p.pos, d, p.last_hit, o - 1u, walk_kind(p.pos, d) == 1);
+            } else if (lc.in) {
+                store_photon(a, pid, p);
+            }
+        }
+        return;
+    }
     // grid-stride (device-driven steps launch one grid for any queue length)
     for (int id = blockIdx.x * BLOCK + threadIdx.x; id < n; id += gridDim.x * BLOCK) {
         const unsigned long long m = masks[id >> 6];
@@ -4327,6 +4442,7 @@ struct StepVariant {
     trace_fn trace = nullptr;       // one-step launches: trace_kernel + shade (nullptr: fn)
     trace_fn trace_gather = nullptr;   // its form refilling from the photon arrays (no ray records)
     propagate_step_fn shade = nullptr;
+    propagate_step_fn shade_live = nullptr;   // its live-record form (shade_kernel's LIVE; nullptr: none)
     int trace_waves = 4;            // waves per SIMD of the trace kernel (persistent grid size)
     int trace_block = BLOCK;        // its workgroup size
     propagate_step_fn tail = nullptr;   // multi-step launches: group-walk kernel (nullptr: fn)
@@ -4377,6 +4493,9 @@ static StepVariant select_step_variant(const chr_geometry *g) {
             sv.trace = trace_kernel<false, 6, 12, 4, 48>;
             sv.trace_gather = trace_kernel<false, 6, 12, 4, 48, true>;
             sv.shade = wires ? shade_kernel<3> : shade_kernel<3, false>;
+            if (v == 0) {   // live records: the default variant only
+                sv.shade_live = wires ? shade_kernel<3, true, true> : shade_kernel<3, false, true>;
+            }
             sv.tail = wires ? propagate_tail_kernel<kTailWaves> : propagate_tail_kernel<kTailWaves, false>;
             sv.tail_group = 8;
             sv.binned = v == 7 ? 1 : (v == 8 ? 0 : 2);
@@ -4387,6 +4506,8 @@ static StepVariant select_step_variant(const chr_geometry *g) {
         const int sb = (int)(SHADE_PHYS_WORDS * 4), tb = (int)(TAIL_PHYS_WORDS * 4);
         (void)hipFuncSetAttribute((const void *)shade_kernel<3>, hipFuncAttributeMaxDynamicSharedMemorySize, sb);
         (void)hipFuncSetAttribute((const void *)shade_kernel<3, false>, hipFuncAttributeMaxDynamicSharedMemorySize, sb);
+        (void)hipFuncSetAttribute((const void *)shade_kernel<3, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, sb);
+        (void)hipFuncSetAttribute((const void *)shade_kernel<3, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, sb);
         (void)hipFuncSetAttribute((const void *)propagate_tail_kernel<kTailWaves>,
                                   hipFuncAttributeMaxDynamicSharedMemorySize, tb);
         (void)hipFuncSetAttribute((const void *)propagate_tail_kernel<kTailWaves, false>,
@@ -4423,6 +4544,7 @@ static int launch_chunk(const chr_geometry *g, const chr_photons *ph, uint32_t *
     a.mode = nullptr;
     a.want = STEP_ONE;
     a.work = nullptr;
+    a.live = nullptr;
     a.prio = 0;
     a.pair = pair_walk_enabled() ? 1u : 0u;
     a.walk_up = walk_up_mode();
@@ -4434,7 +4556,7 @@ static int launch_chunk(const chr_geometry *g, const chr_photons *ph, uint32_t *
     hipLaunchKernelGGL(scatter_queue_kernel, dim3(grid_for(nthreads)), dim3(BLOCK), 0, stream, masks, offsets, bsums,
                        counters + 1, in_queue, first, nthreads, out_queue,
                        RayEnrol{nullptr, nullptr, nullptr, nullptr}, (const uint32_t *)nullptr,
-                       (const uint32_t *)nullptr, STEP_IDLE);
+                       (const uint32_t *)nullptr, STEP_IDLE, LiveCarry{nullptr, nullptr, nullptr, a});
     CHR_HIP_CHECK(hipGetLastError());
     return CHR_OK;
 }
@@ -4461,6 +4583,9 @@ struct FlatCtx {
     // step's classification, then every step's scatter for the next step),
     // rays_walk the binned first step's records permuted into walk order
     uint4 *rays = nullptr, *rays_walk = nullptr;
+    // the live records (shade_kernel's LIVE): two buffers of one record per photon, slot k's
+    // queue in live[k & 1]
+    uint4 *live[2] = {nullptr, nullptr};
 };
 static int flat_get(uint32_t n, FlatCtx &fc, int ctx = 0) {
     static thread_local Scratch s[NCTX][16];
@@ -4505,6 +4630,13 @@ static uint32_t walk_up_mode() {
     return e && (e[0] == '0' || e[0] == '2' || e[0] == '4') ? (uint32_t)(e[0] - '0') : 1u;
 }
 
+// CHR_LIVE_RECORDS=0: every one-step slot reads and writes the photon arrays (A/B; default:
+// the device-driven slots of the default variant carry live records, shade_kernel's LIVE)
+static bool live_records_enabled() {
+    const char *e = getenv("CHR_LIVE_RECORDS");
+    return !(e && e[0] == '0');
+}
+
 static int slot_timing() {
     const char *e = getenv("CHR_SLOT_TIMING");
     if (!e || e[0] == 't') return 1;
@@ -4538,6 +4670,8 @@ struct SlotCtl {
     // on the batch stream after prefix_done, starting with ev_rest0
     int phase = 0;
     int ctx = 0;                      // buffer context (walk-stack column)
+    int slot = 0;                     // the slot's index in its propagate
+    bool live = false;                // the propagate's one-step slots carry live records (device_slots)
     uint32_t *host_ring = nullptr;    // pinned (mode, length) words the head kernel writes (nullptr: none)
     // the next slot's head folded into this slot's block-sum scan (fold_head: every slot
     // after the first then launches no head kernel of its own); next_head.ray_counter is
@@ -4594,10 +4728,12 @@ static int launch_step(const chr_geometry *g, const chr_photons *ph, uint32_t *r
     a.mode = mode;
     a.want = STEP_ONE;
     a.work = nullptr;
+    a.live = nullptr;
     a.prio = 0;
     a.pair = pair_walk_enabled() ? 1u : 0u;
     a.walk_up = walk_up_mode();
     RayEnrol fe{nullptr, nullptr, nullptr, nullptr};
+    LiveCarry lc{nullptr, nullptr, nullptr, a};
     const uint32_t threads = std::min(cap, (n + 63u) & ~63u);
     const StepVariant sv = select_step_variant(g);
     // host-driven: the split when this launch is one step; device-driven: the
@@ -4695,8 +4831,18 @@ static int launch_step(const chr_geometry *g, const chr_photons *ph, uint32_t *r
         }
         a.hits = hits;
         a.max_steps = 1;
+        propagate_step_fn shade = sv.shade;
+        if (sc && sc->live) {   // live records: this slot's buffer (none in the first), the other one the next slot's
+            if (!use_rays || !fc->live[0] || !sv.shade_live)
+                return chr::fail(CHR_ERR_INVALID, "launch_step: live records need the ray records and their buffers");
+            if (sc->slot > 0) {
+                a.live = fc->live[sc->slot & 1];
+                shade = sv.shade_live;
+            }
+            lc = LiveCarry{a.live, fc->live[(sc->slot + 1) & 1], hn.mode, a};
+        }
         if (sc && sc->rng_ready) CHR_HIP_CHECK(hipStreamWaitEvent(stream, sc->rng_ready, 0));
-        hipLaunchKernelGGL(sv.shade, dim3(grid_for(threads)), dim3(BLOCK), phys_lds_bytes(g->dev, SHADE_PHYS_WORDS), stream,
+        hipLaunchKernelGGL(shade, dim3(grid_for(threads)), dim3(BLOCK), phys_lds_bytes(g->dev, SHADE_PHYS_WORDS), stream,
                            (const DevGeom *)g->d_dev, a, cap);
     }
     if (split_out) *split_out = split;
@@ -4737,7 +4883,7 @@ static int launch_step(const chr_geometry *g, const chr_photons *ph, uint32_t *r
                          hnp);
         hipLaunchKernelGGL(scatter_queue_kernel, dim3(std::min<uint32_t>(4096u, grid_for(n))), dim3(BLOCK), 0, stream,
                            masks, offsets, bsums, counters + 1, in_queue, 0, (int32_t)n, out_queue, fe, dev_n, mode,
-                           STEP_TAIL);
+                           STEP_TAIL, lc);
         CHR_HIP_CHECK(hipGetLastError());
         return CHR_OK;
     }
@@ -4758,7 +4904,7 @@ static int launch_step(const chr_geometry *g, const chr_photons *ph, uint32_t *r
     launch_mask_scan(masks, nwords, offsets, bsums, out_queue, counters + 1, nullptr, stream, dev_n, mode, STEP_IDLE, hnp);
     hipLaunchKernelGGL(scatter_queue_kernel, dim3(sc ? std::min<uint32_t>(4096u, grid_for(n)) : grid_for(n)), dim3(BLOCK),
                        0, stream, masks, offsets, bsums, counters + 1, in_queue, 0, (int32_t)n, out_queue, fe, dev_n,
-                       mode, STEP_IDLE);
+                       mode, STEP_IDLE, lc);
     CHR_HIP_CHECK(hipGetLastError());
     return CHR_OK;
 }
@@ -4855,6 +5001,7 @@ struct PropBufs {
     unsigned long long *tail_masks = nullptr;
     uint32_t *pinned = nullptr;
     FlatCtx fc{};
+    bool live = false;       // the last device-driven propagate carried live records (device_slots)
 };
 
 static int prop_bufs(uint32_t nphotons, int32_t ntpb, int32_t max_blocks, int ctx, bool tail_masks, PropBufs &b) {
@@ -4869,7 +5016,9 @@ static int prop_bufs(uint32_t nphotons, int32_t ntpb, int32_t max_blocks, int ct
     const size_t hbytes = b.fused ? (size_t)nphotons * 24 + 128 + 256 + 512 + sort_temp_bytes16(nphotons) : 0;
     // split path: ray records, queue order + walk order (FlatCtx::rays / rays_walk)
     const size_t rbytes = b.fused ? (size_t)nphotons * 64 + 512 : 0;
-    const size_t base_bytes = 2 * qbytes + swords * 4 + 64 + hbytes + rbytes;
+    // split path: live records, two buffers of 64 B per photon (FlatCtx::live)
+    const size_t lbytes = b.fused ? (size_t)nphotons * 128 + 512 : 0;
+    const size_t base_bytes = 2 * qbytes + swords * 4 + 64 + hbytes + rbytes + lbytes;
     const size_t mbytes = tail_masks ? ((size_t)nphotons + 63) / 64 * 8 + 512 : 0;
     void *buf = nullptr;
     int rc = scratch_get(base_bytes + mbytes, &buf, ctx);
@@ -4887,6 +5036,8 @@ static int prop_bufs(uint32_t nphotons, int32_t ntpb, int32_t max_blocks, int ct
     if (b.fused) {
         b.fc.rays = (uint4 *)(((uintptr_t)buf + 2 * qbytes + swords * 4 + 64 + hbytes + 255) & ~(uintptr_t)255);
         b.fc.rays_walk = b.fc.rays + 2 * (size_t)nphotons;
+        b.fc.live[0] = (uint4 *)(((uintptr_t)(b.fc.rays_walk + 2 * (size_t)nphotons) + 255) & ~(uintptr_t)255);
+        b.fc.live[1] = b.fc.live[0] + LIVE_QUADS * (size_t)nphotons;
     }
     return CHR_OK;
 }
@@ -4937,6 +5088,8 @@ static int device_slots(const chr_geometry *g, const chr_photons *ph, uint32_t n
     uint32_t *done = ctl + 2 * (size_t)max_steps;
     if (!run.prefix_done) CHR_HIP_CHECK(hipMemsetAsync(done, 0, 4, stream));
     b.fc.enrol_next = true;
+    // live records: the default variant's slots, each photon once (use_weights runs the tail at once)
+    b.live = live_records_enabled() && !use_weights && select_step_variant(g).shade_live && b.fc.live[0];
     uint32_t *ring = b.pinned + 64;   // (mode, n) of recent slots, 32 entries (written by each slot's head kernel)
     // slot k + 1's head runs at the end of slot k's scan (no head dispatch per slot)
     const bool fold = true;
@@ -4955,6 +5108,8 @@ static int device_slots(const chr_geometry *g, const chr_photons *ph, uint32_t n
         sc.evt_tail1 = timing == 2 ? ev[6] : nullptr;
         sc.rng_ready = k == 0 ? run.rng_ready : nullptr;
         sc.ctx = run.ctx;
+        sc.slot = k;
+        sc.live = b.live;
         sc.host_ring = ring + 2 * (k % 32);   // written by the slot's head kernel (slot 0 of a batch: its prefix's)
         sc.fold_head = fold;
         if (fold && k + 1 < max_steps)
@@ -4994,10 +5149,11 @@ static int device_slots(const chr_geometry *g, const chr_photons *ph, uint32_t n
 // per-slot statistics of a finished device-driven propagate (h: [mode, length]
 // per slot); prefixed: slot 0 ran as prefix + rest (chr_propagate_batches)
 static int slot_stats(chr_propagate_stats &st, const uint32_t *h, int k, const std::vector<hipEvent_t> &events,
-                      bool tail_stream, bool prefixed = false) {
+                      bool tail_stream, bool live, bool prefixed = false) {
     const int timing = slot_timing();
     for (int j = 0; j < k; ++j) {
         const uint32_t m = h[2 * j], nj = h[2 * j + 1];
+        if (live && j >= 1 && m == STEP_ONE) st.live_record_slots++;
         const hipEvent_t *ev = events.data() + SLOT_EVENTS * (size_t)j;
         float ms = 0.0f;
         if (timing < 2) {   // (CHR_SLOT_TIMING) counts only, and the trace launches' times
@@ -5182,7 +5338,7 @@ extern "C" int chr_propagate(const chr_geometry *g, const chr_photons *ph, uint3
         std::vector<uint32_t> h(2 * (size_t)k);
         CHR_HIP_CHECK(hipMemcpy(h.data(), ctl, 8 * (size_t)k, hipMemcpyDeviceToHost));
         if ((rc = timing_events(0, &evp))) return rc;
-        if ((rc = slot_stats(st, h.data(), k, *evp, false))) return rc;
+        if ((rc = slot_stats(st, h.data(), k, *evp, false, b.live))) return rc;
         step = max_steps;   // as the host loop: it leaves early only on an empty queue
         n = 0;
     }
@@ -5439,6 +5595,7 @@ static int propagate_batches(const chr_geometry *g, const chr_photons *phs, cons
                             max_steps, use_weights, scatter_first, bufs[c], c, bh[j].ev, bh[j].prefix_done, ps);
     };
     std::vector<int> slots(nb, 0);
+    std::vector<char> live(nb, 0);
     for (size_t j = 0; j < nb; ++j) {
         CHR_TRY(prefix(j));
         const uint32_t i = idx[j];
@@ -5453,6 +5610,7 @@ static int propagate_batches(const chr_geometry *g, const chr_photons *phs, cons
         uint32_t *ctl = nullptr;
         CHR_TRY(device_slots(g, phs + i, nphotons[i], d_rng_states, rng_nslots, ntpb, max_steps, use_weights,
                              scatter_first, b, run, stream, &ctl, &slots[j]));
+        live[j] = b.live;
         // after the batch's last slot (and every tail before it on ts): read its counters back
         CHR_HIP_CHECK(hipStreamWaitEvent(ts, bh[j].ev[SLOT_EVENTS * (size_t)(slots[j] - 1) + 4], 0));
         CHR_HIP_CHECK(hipMemcpyAsync(bh[j].pinned + 128, ctl, 8 * (size_t)slots[j], hipMemcpyDeviceToHost, ts));
@@ -5463,7 +5621,7 @@ static int propagate_batches(const chr_geometry *g, const chr_photons *phs, cons
     CHR_HIP_CHECK(hipEventSynchronize(bh[nb - 1].done));
     for (size_t j = 0; j < nb; ++j) {
         chr_propagate_stats st{};
-        CHR_TRY(slot_stats(st, bh[j].pinned + 128, slots[j], bh[j].ev, true, true));
+        CHR_TRY(slot_stats(st, bh[j].pinned + 128, slots[j], bh[j].ev, true, live[j] != 0, true));
         PropBufs view;
         view.fused = true;
         view.pinned = bh[j].pinned;

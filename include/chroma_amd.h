@@ -174,7 +174,7 @@ typedef struct chr_propagate_stats {
     uint64_t wave_step_cycles;    /* whole photon step loops; counting variant only */
     double trace_ms;              /* device time of the BVH-walk kernel (trace_kernel) alone, HIP events */
     uint32_t trace_launches;      /* one-step launches walked by trace_kernel */
-    uint32_t reserved;
+    uint32_t live_record_slots;   /* one-step slots whose shade_kernel read live records (CHR_LIVE_RECORDS) */
     uint64_t trace_rays;          /* queued photons handed to those launches */
     uint32_t trace_ms_n;          /* entries of trace_launch_ms filled (first CHR_TRACE_MS_MAX launches) */
     float trace_launch_ms[32];    /* device time of each trace_kernel launch, in order */
