@@ -97,6 +97,12 @@ _SIGNATURES = {
     'chr_geometry_phys_words': (c_i32, [c_vp, ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_uint32)]),
     'chr_init_rng': (c_i32, [c_vp, c_u32, c_u64, c_u64, c_vp]),
     'chr_rng_download': (c_i32, [c_vp, c_u32, c_vp, c_vp]),
+    'chr_gensteps_count': (c_i32, [c_vp, c_u32, ctypes.POINTER(c_u64)]),
+    'chr_generate_photons': (c_i32, [c_vp, c_vp, c_u32, ctypes.POINTER(PhotonsDesc), c_u32, c_u32, c_vp, c_u32,
+                                     ctypes.POINTER(c_u32), ctypes.POINTER(c_u32), c_vp]),
+    'chr_generate_photons_host': (c_i32, [ctypes.POINTER(GeometryDesc), c_vp, c_u32, ctypes.POINTER(PhotonsDesc),
+                                          c_u32, c_u32, c_vp, c_u32, ctypes.POINTER(c_u32), ctypes.POINTER(c_u32)]),
+    'chr_init_rng_host': (c_i32, [c_vp, c_u32, c_u64, c_u64, c_u64]),
     'chr_propagate_scratch_words': (c_u64, [c_u32]),
     'chr_propagate_chunk': (c_i32, [c_vp, ctypes.POINTER(PhotonsDesc), c_vp, c_u32, c_i32, c_i32, c_vp, c_vp,
                                     c_i32, c_i32, c_i32, c_vp, c_vp]),

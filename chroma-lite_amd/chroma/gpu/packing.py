@@ -81,6 +81,7 @@ class PackedGeometry(object):
         if len(materials) > 127 or len(surfaces) > 127:
             raise ValueError('at most 127 materials and 127 surfaces fit the 8-bit material codes')
 
+        self.material_objects = materials     # index = the material index of the device tables
         self.materials = []
         for m in materials:
             if m is None:

@@ -291,3 +291,35 @@ def propagate_batches(photon_batches, gpu_geometry, rng_states, nthreads_per_blo
             print('WARNING: %d BVH traversals exceeded the 1000-entry stack' % st.stack_overflows, file=sys.stderr)
         out.append(st)
     return out
+
+
+def generate_photons(gensteps, gpu_geometry, rng_states, out=None, first_photon=0):
+    """Photons of `gensteps` (chroma.gensteps.Gensteps, or GENSTEP_DTYPE records
+    with material indices) drawn on the device by chr_generate_photons: photon
+    k by RNG slot k mod len(rng_states), in step-major order; rng_states is
+    advanced.  Returns a GPUPhotonsSlice of the generated photons whose
+    `exhausted` attribute counts the Cherenkov photons whose rejection loop ran
+    out (emitted at the wavelength of the largest n).  out: GPUPhotons to write
+    into from `first_photon` on (default: fresh arrays); the slice is then a
+    view of out[first_photon : first_photon + n]."""
+    from chroma import gensteps as gs
+    packed = getattr(gpu_geometry, 'packed', None)
+    rec = gs._as_records(gensteps, getattr(packed, 'material_objects', None))
+    n = int(rec['nphotons'].astype(np.uint64).sum())
+    if n > 2 ** 31 - 1:
+        raise ValueError('%d photons: one call generates at most 2^31 - 1' % n)
+    first_photon = int(first_photon)
+    if out is None:
+        holder = type('H', (), _alloc(first_photon + n))()
+    else:
+        holder = out
+    capacity = holder.pos.size
+    ngen, exhausted = ctypes.c_uint32(), ctypes.c_uint32()
+    _native.call('chr_generate_photons', ctypes.c_void_p(gpu_geometry.gpudata), rec.ctypes.data, len(rec),
+                 ctypes.byref(_photons_desc(holder)), first_photon, capacity, rng_states.gpudata, len(rng_states),
+                 ctypes.byref(ngen), ctypes.byref(exhausted), current_stream())
+    w = slice(first_photon, first_photon + ngen.value)
+    made = GPUPhotonsSlice(*[getattr(holder, f)[w] for f in ('pos', 'dir', 'pol', 'wavelengths', 't',
+                                                            'last_hit_triangles', 'flags', 'weights', 'evidx')])
+    made.exhausted = exhausted.value
+    return made

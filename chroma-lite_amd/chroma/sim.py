@@ -14,6 +14,7 @@ import numpy as np
 
 from chroma import event
 from chroma import gpu
+from chroma.gensteps import Gensteps
 from chroma.gpu import gpuarray as ga
 from chroma.itertoolset import peek
 
@@ -79,6 +80,14 @@ class Simulation(object):
         self.rng_states = gpu.get_rng_states(self.nthreads_per_block * self.max_blocks, seed=self.seed)
         self.pdf_config = None
         self.last_pipeline = None     # (batches, propagate_batches calls) of the last simulate()
+
+    def generate(self, gensteps):
+        """The photons of a Gensteps, drawn on the device with rng_states
+        (chroma.gpu.generate_photons); `last_exhausted` counts the Cherenkov
+        photons whose rejection loop ran out."""
+        made = gpu.generate_photons(gensteps, self.gpu_geometry, self.rng_states)
+        self.last_exhausted = made.exhausted
+        return made
 
     # ------------------------------------------------------------ batch stages
     def _upload(self, batch_events):
@@ -205,11 +214,17 @@ class Simulation(object):
         and yielded in order; up to pipeline_batches closed batches are
         propagated in one pipelined call (read ahead from the iterable), with
         results bit-identical to the reference's one-batch-at-a-time loop."""
-        if isinstance(iterable, event.Photons):
+        if isinstance(iterable, (event.Photons, Gensteps)):
             first, iterable = iterable, [iterable]
         else:
             first, iterable = peek(iterable)
-        if isinstance(first, event.Photons):
+        if isinstance(first, Gensteps):
+            # one event per Gensteps: its photons are drawn on the device with this
+            # simulation's rng_states, in input order as the events are read (a pipelined
+            # run reads ahead, so every batch of a propagate call is generated before it),
+            # and enter as a GPU-resident source (_stack_gpu_photon_sources)
+            iterable = (event.Event(photons_beg=self.generate(x)) for x in iterable)
+        elif isinstance(first, event.Photons):
             iterable = (event.Event(photons_beg=x) for x in iterable)
         elif isinstance(first, event.Vertex):
             raise NotImplementedError('Vertex input not supported in Chroma')
@@ -295,6 +310,12 @@ class ShardedSimulation(Simulation):
         if self.rank:
             self.rng_states = gpu.get_rng_states(nslots, seed=self.seed, first_subsequence=self.rank * nslots)
         self._torch = torch
+
+    def generate(self, gensteps):
+        # every rank must see the same photons of an event, and the ranks' rng_states are
+        # different streams: generate with Simulation (or chroma.gpu.generate_photons from
+        # states seeded alike on every rank) and pass the photons
+        raise NotImplementedError('Gensteps input is not sharded: generate the photons first')
 
     def _upload(self, batch_events):
         from chroma.gpu import shard

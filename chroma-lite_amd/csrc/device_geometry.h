@@ -103,6 +103,11 @@ struct chr_geometry {
     // rest waits here until chr_geometry_ref_nodes() uploads it (once).
     std::vector<uint4> *h_ref_nodes;
     bool ref_tri_pending;   // the 48-byte reference triangle records are built on first use
+    // host copies for the genstep validation (chr_generate_photons works out each Cherenkov
+    // step's n_max before any launch): every material's refractive_index table
+    // ([nmaterials][wl_n + 1]) and component count
+    std::vector<float> *h_refractive_index;
+    std::vector<uint32_t> *h_num_comp;
 };
 namespace chr {
 // the bucket index of ncomp CDFs of n entries (CDF c at cdf0 + c * stride):

@@ -105,6 +105,8 @@ extern "C" int chr_geometry_destroy(chr_geometry *g) {
     for (int i = 0; i < g->nallocs; ++i) (void)hipFree(g->allocs[i]);
     (void)hipSetDevice(prev);
     delete g->h_ref_nodes;
+    delete g->h_refractive_index;
+    delete g->h_num_comp;
     delete g;
     return CHR_OK;
 }
@@ -374,6 +376,8 @@ static int geometry_create(const chr_geometry_desc *d, const chr_wide_bvh_desc *
         Blob blob, comp;
         const uint32_t W1 = d->wavelength_n + 1, T1 = d->time_n + 1;
         std::vector<chr::DevMaterial> mats(d->nmaterials);
+        g->h_refractive_index = new std::vector<float>((size_t)d->nmaterials * W1);
+        g->h_num_comp = new std::vector<uint32_t>(d->nmaterials);
         for (uint32_t i = 0; i < d->nmaterials; ++i) {
             const chr_material_desc &m = d->materials[i];
             chr::DevMaterial &o = mats[i];
@@ -382,6 +386,8 @@ static int geometry_create(const chr_geometry_desc *d, const chr_wide_bvh_desc *
                 throw rc;
             }
             o.num_comp = m.num_comp;
+            (*g->h_num_comp)[i] = m.num_comp;
+            std::memcpy(g->h_refractive_index->data() + (size_t)i * W1, m.refractive_index, (size_t)W1 * 4);
             o.refractive_index = blob.add(m.refractive_index, W1);
             o.absorption_length = blob.add(m.absorption_length, W1);
             o.scattering_length = blob.add(m.scattering_length, W1);

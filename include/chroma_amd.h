@@ -144,6 +144,75 @@ int chr_init_rng_subseq(uint32_t *d_states, uint32_t nslots, uint64_t seed, uint
 /* copy slot states to the host (tests; 6*nslots words, SoA) */
 int chr_rng_download(const uint32_t *d_states, uint32_t nslots, uint32_t *h_out, void *stream);
 
+/* ---------------------------------------------------------------- gensteps
+ * A genstep is "a charged particle made nphotons photons along this segment":
+ * the compact record a particle simulation writes (Opticks' term) and the
+ * device turns into photons.  replaces: the reference's Geant4 light source
+ * (chroma/generator/, bin/chroma-sim), which needs a host particle simulation
+ * per photon; here the caller supplies the yield (nphotons) and the device
+ * draws the photons.  64 bytes, 16 words.
+ *
+ * Photons are numbered step-major (photon k of the call belongs to the step i
+ * with offset[i] <= k < offset[i+1], offset = exclusive prefix sum of
+ * nphotons).  Photon k is drawn by RNG slot k mod rng_nslots; a slot draws its
+ * photons in ascending k, so the result depends on the slot states, rng_nslots
+ * and the records only.  Draw order of one photon (csrc/genstep.h), every
+ * multiply-add an explicit fmaf:
+ *   f = uniform01
+ *   pos = fma(f, dx, x0) per component, t = fma(f, dt, t0)
+ *   weight = 1, last_hit = -1, evidx = the record's
+ *   CHR_GEN_ISOTROPIC:     dir = uniform_sphere (2 draws); a = uniform_sphere (2 draws),
+ *                          pol = cross(a, dir) / |cross(a, dir)|;
+ *                          wavelength = wl_lo + uniform01 * (wl_hi - wl_lo); flags = 0
+ *   CHR_GEN_SCINTILLATION: wavelength = sample_cdf(material's comp_reemission_wvl_cdf[component]) (1 draw);
+ *                          t += sample_cdf(comp_reemission_time_cdf[component]) (1 draw);
+ *                          dir, pol as ISOTROPIC (4 draws); flags = CHR_SCINTILLATION
+ *   CHR_GEN_CHERENKOV:     u = dx / |dx|; at most CHR_GEN_MAX_TRIES times:
+ *                            1/wl = 1/wl_hi + uniform01 * (1/wl_lo - 1/wl_hi), n = refractive_index(wl)
+ *                            (the propagate kernels' interp_property), c = 1 / (beta * n),
+ *                            accept when 1 - c*c > uniform01 * s2max, s2max = 1 - 1/(beta * n_max)^2
+ *                            with n_max the largest n over [wl_lo, wl_hi];
+ *                          tries used up: wl = the wavelength of n_max (counted in *exhausted);
+ *                          phi = uniform01 * 2 pi (1 draw); s = sqrt(1 - c*c);
+ *                          (e1, e2): a = the coordinate axis of u's smallest |component| (x before y
+ *                          before z on ties), e1 = cross(u, a) / |cross(u, a)|, e2 = cross(u, e1);
+ *                          w = cos(phi) e1 + sin(phi) e2; dir = c u + s w;
+ *                          pol = normalise(c dir - u), evaluated as normalise(c w - s u) (the same
+ *                          vector divided by s, without the cancellation); flags = CHR_CHERENKOV */
+enum chr_genstep_kind { CHR_GEN_ISOTROPIC = 0, CHR_GEN_SCINTILLATION = 1, CHR_GEN_CHERENKOV = 2 };
+#define CHR_GEN_MAX_TRIES 1024
+typedef struct chr_genstep {
+    uint32_t kind, nphotons, material, evidx;   /* chr_genstep_kind; material: index into the geometry's */
+    float x0[3], t0;                             /* start of the segment (mm, ns) */
+    float dx[3], dt;                             /* its extent: photons start at x0 + f dx, t0 + f dt */
+    float wl_lo, wl_hi, beta;                    /* wavelength range (nm; ISOTROPIC, CHERENKOV); v/c (CHERENKOV) */
+    uint32_t component;                          /* scintillation component (SCINTILLATION) */
+} chr_genstep;
+
+/* *total = sum of nphotons (64-bit: may exceed what one call generates) */
+int chr_gensteps_count(const chr_genstep *h_steps, uint32_t nsteps, uint64_t *total);
+/* Generate the steps' photons into out[first_photon, first_photon + total) (arrays of >= capacity
+ * photons; first_photon + total <= capacity) with the slot states d_rng_states, which are advanced.
+ * All nine fields are written.  Every record is validated on the host before any launch
+ * (CHR_ERR_INVALID: unknown kind, material >= nmaterials, SCINTILLATION component >= num_comp,
+ * a non-finite field, wl_lo > wl_hi or a non-positive limit, CHERENKOV with |dx| = 0, beta outside
+ * (0, 1] or beta * n_max <= 1, total > capacity - first_photon or > 2^31 - 1, rng_nslots = 0).
+ * *ngenerated = total, *exhausted = photons whose rejection loop ran out.  Synchronous. */
+int chr_generate_photons(const chr_geometry *g, const chr_genstep *h_steps, uint32_t nsteps,
+                         const chr_photons *out, uint32_t first_photon, uint32_t capacity,
+                         uint32_t *d_rng_states, uint32_t rng_nslots, uint32_t *ngenerated,
+                         uint32_t *exhausted, void *stream);
+/* The same on the host (no GPU needed), over a geometry descriptor: out holds HOST arrays of
+ * >= first_photon + total photons, h_rng_states host slot states in the device's SoA layout.
+ * Bit-identical to chr_generate_photons (one source, csrc/genstep.h). */
+int chr_generate_photons_host(const chr_geometry_desc *desc, const chr_genstep *h_steps, uint32_t nsteps,
+                              const chr_photons *out, uint32_t first_photon, uint32_t capacity,
+                              uint32_t *h_rng_states, uint32_t rng_nslots, uint32_t *ngenerated,
+                              uint32_t *exhausted);
+/* chr_init_rng_subseq on the host: the same states in the same SoA layout */
+int chr_init_rng_host(uint32_t *h_states, uint32_t nslots, uint64_t seed, uint64_t first_subsequence,
+                      uint64_t offset);
+
 /* -------------------------------------------------------------- propagate */
 /* replaces: the `propagate` kernel (chroma/cuda/propagate.cu:254-366), one
  * chunk launch: slots [0, nthreads), photon = d_input_queue[first_photon + slot].
