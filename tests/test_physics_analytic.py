@@ -26,6 +26,13 @@ frequencies / distributions are compared with the analytic answer.
     surface's reemission CDF (linear between grid points, sample_cdf,
     random.h:34-55), directions are isotropic.
 
+The sibling module test_physics_closed_forms.py pins the rest with this
+module's helpers: the Rayleigh scattering law (photon.h:400-453),
+multi-component bulk re-emission (496-540), the DICHROIC (877-907), ANGULAR
+(909-951) and default (967-1035) surface models, the use_weights /
+scatter_first weighting (459-494, 541-568, and at those surfaces), and the
+analytic FP64 wire planes (108-277).
+
 Each test runs on the HIP path (-m gpu) and on the CPU oracle (its own
 restatement, so the oracle is pinned every CPU run).  Statistical checks:
 binomial / chi-square / KS p-values above 1e-3 at fixed seeds (the photons are
@@ -87,22 +94,27 @@ def _photons(pos, d, pol, wl=400.0):
     return Photons(pos, d, np.asarray(pol, np.float32), np.full(n, wl, np.float32), np.zeros(n, np.float32))
 
 
-def _propagate(backend, geo, photons, max_steps=1, seed=1, request=None):
-    """One propagate of `photons` in `geo`; returns the end photons (numpy fields)."""
+def _propagate(backend, geo, photons, max_steps=1, seed=1, request=None, use_weights=False, scatter_first=0):
+    """One propagate of `photons` in `geo`; returns the end photons (numpy fields).
+    The photons start with weight 1; a weighted run (use_weights / scatter_first)
+    uploads those weights, a plain one leaves the device's fill of 1."""
     from chroma.gpu.packing import PackedGeometry
+    weighted = bool(use_weights) or scatter_first != 0
     if backend == 'hip':
         request.getfixturevalue('cuda')
         from chroma import gpu
         rng = gpu.get_rng_states(NTPB * MAXB, seed=seed)
-        gp = gpu.GPUPhotons(photons, copy_flags=True, copy_triangles=False, copy_weights=False)
-        gp.propagate(gpu.GPUGeometry(geo), rng, nthreads_per_block=NTPB, max_blocks=MAXB, max_steps=max_steps)
+        gp = gpu.GPUPhotons(photons, copy_flags=True, copy_triangles=False, copy_weights=weighted)
+        gp.propagate(gpu.GPUGeometry(geo), rng, nthreads_per_block=NTPB, max_blocks=MAXB, max_steps=max_steps,
+                     use_weights=use_weights, scatter_first=scatter_first)
         return gp.get()
     host = oracle.HostPhotons(photons)
     host.flags[:] = 0
     host.last_hit_triangles[:] = -1
     host.weights[:] = 1
     st = oracle.rng_init(NTPB * MAXB, seed=seed)
-    oracle.propagate(PackedGeometry(geo), host, st, NTPB * MAXB, NTPB, MAXB, max_steps)
+    oracle.propagate(PackedGeometry(geo), host, st, NTPB * MAXB, NTPB, MAXB, max_steps,
+                     use_weights=use_weights, scatter_first=scatter_first)
     return host
 
 
