@@ -145,7 +145,9 @@ _SIGNATURES = {
     'chr_daq_acquire': (c_i32, [ctypes.POINTER(PhotonsDesc), c_vp, c_u32, c_vp, c_u32, c_i32, c_i32, c_vp, c_vp,
                                 c_vp, c_vp, c_vp, c_i32, c_i32, c_f32, c_i32, c_i32, c_vp]),
     'chr_daq_end': (c_i32, [c_vp, c_vp, c_vp, c_vp, c_u32, c_i32, c_f32, c_vp]),
-    'chr_init_rng_subseq': (c_i32, [c_vp, c_u32, c_u64, c_u64, c_u64, c_vp]),
+    'chr_daq_acquire_events': (c_i32, [ctypes.POINTER(PhotonsDesc), c_i32, c_vp, c_i32, c_vp, c_u32, c_u32, c_vp,
+                                       c_vp, c_vp, c_vp, c_vp, c_vp, c_f32, c_i32, c_i32, c_vp]),
+    'chr_init_rng_subseq':(c_i32, [c_vp, c_u32, c_u64, c_u64, c_u64, c_vp]),
     'chr_channel_hit_counts': (c_i32, [ctypes.POINTER(PhotonsDesc), c_i32, c_i32, c_u32, c_vp, c_vp, c_vp, c_i32,
                                        c_vp]),
     'chr_pdf_bin_hits': (c_i32, [c_i32, c_vp, c_vp, c_vp, c_i32, c_f32, c_f32, c_i32, c_f32, c_f32, c_vp, c_vp]),

@@ -4,11 +4,13 @@ The DAQ turns detected photons into per-channel readout: earliest time
 (photon time + a sample of the detector's time CDF), integrated charge (a
 sample of the charge CDF, quantised by charge_unit) and the OR of the photon
 histories.  Kernels: csrc/daq.hip through the C ABI (chr_daq_begin /
-chr_daq_acquire / chr_daq_end); no host fallback.
+chr_daq_acquire / chr_daq_end, and chr_daq_acquire_events for all events of a
+batch in one call); no host fallback.
 """
 import ctypes
 
 import numpy as np
+import torch
 
 from chroma import event
 from chroma.gpu import _native
@@ -40,6 +42,44 @@ class GPUChannels(object):
 
     def __len__(self):
         return self.t.size
+
+
+class GPUEventChannels(object):
+    """The rows GPUDaq.acquire_events left on the device, nevents x nchannels each
+    and row e = event e: time_int (u32, the f32 earliest times' bit patterns),
+    q_int (u32 quantised charge), flags (u32 history) and q (f32 charge).  They
+    are views of arrays the GPUDaq reuses: valid until its next acquire_events."""
+
+    def __init__(self, time_int, q_int, flags, q, nevents, nchannels, host=None):
+        self.time_int = time_int
+        self.q_int = q_int
+        self.flags = flags
+        self.q = q
+        self.nevents = nevents
+        self.nchannels = nchannels
+        self._host = host
+
+    def get(self):
+        """One event.Channels per event (hit = earliest time below 1e8, as
+        GPUChannels.get).  t, q and flags are downloaded once each, through
+        pinned host memory, and every event owns copies of its rows."""
+        n = self.nevents * self.nchannels
+        if n == 0:
+            return []
+        host = self._host(3 * n)        # the GPUDaq's pinned words, grown on demand
+        for k, a in enumerate((self.time_int, self.q, self.flags)):
+            host[k * n:(k + 1) * n].copy_(a.tensor.view(torch.int32), non_blocking=True)
+        torch.cuda.current_stream().synchronize()
+        rows = host[:3 * n].numpy().reshape(3, self.nevents, self.nchannels)
+        out = []
+        for e in range(self.nevents):
+            t = rows[0, e].view(np.float32).copy()
+            out.append(event.Channels(t < 1e8, t, rows[1, e].view(np.float32).copy(),
+                                      rows[2, e].view(np.uint32).copy()))
+        return out
+
+    def __len__(self):
+        return self.nevents
 
 
 class _DetectorDesc(ctypes.Structure):   # chr_daq_detector (include/chroma_amd.h)
@@ -76,6 +116,8 @@ class GPUDaq(object):
         self.nchannels = int(gpu_detector.nchannels)
         self.ndaq = ndaq
         self.stride = gpu_detector.nchannels
+        self._event_rows = None      # acquire_events' device arrays, grown on demand
+        self._event_host = None      # and the pinned host words GPUEventChannels.get stages through
 
     def begin_acquire(self, nthreads_per_block=64):
         """daq.py:56-60: earliest times = 1e9, charges and histories = 0."""
@@ -104,3 +146,39 @@ class GPUDaq(object):
                      self.nchannels, ctypes.c_float(self.charge_unit), current_stream())
         return GPUChannels(self.earliest_time_gpu, self.channel_q_gpu, self.channel_history_gpu, self.ndaq,
                            self.stride)
+
+    def _event_arrays(self, n):
+        if self._event_rows is None or len(self._event_rows[0]) < n:
+            self._event_rows = None          # release before growing
+            self._event_rows = (ga.empty(n, np.uint32), ga.empty(n, np.uint32), ga.empty(n, np.uint32),
+                                ga.empty(n, np.float32))
+        return [a[:n] for a in self._event_rows]
+
+    def _event_host_words(self, n):
+        if self._event_host is None or self._event_host.numel() < n:
+            self._event_host = None
+            self._event_host = torch.empty(n, dtype=torch.int32, pin_memory=True)
+        return self._event_host
+
+    def acquire_events(self, gpuphotons, rng_states, bounds, nthreads_per_block=64, max_blocks=1024, weight=1.0):
+        """begin_acquire / acquire / end_acquire (daq.py:56-101) for every event
+        [bounds[e], bounds[e+1]) of `gpuphotons`, as sim.py:143-152 runs them one
+        after another, in one native call whose launches do not depend on the
+        number of events (chr_daq_acquire_events): the same channel words and
+        the same rng_states afterwards, bit for bit.  Returns a GPUEventChannels
+        of len(bounds) - 1 rows.  ndaq > 1 (run_daq_many) is not batched."""
+        if self.ndaq != 1:
+            raise ValueError('acquire_events runs ndaq = 1 acquisitions only (this GPUDaq has ndaq = %d)' % self.ndaq)
+        bounds = np.ascontiguousarray(bounds, dtype=np.int64)
+        if bounds.ndim != 1 or len(bounds) < 1:
+            raise ValueError('bounds must be a 1-D array of nevents + 1 photon offsets')
+        nevents = len(bounds) - 1
+        t_int, q_int, hist, q = self._event_arrays(nevents * self.nchannels)
+        if nevents == 0:
+            return GPUEventChannels(t_int, q_int, hist, q, 0, self.nchannels, host=self._event_host_words)
+        ph = gpuphotons._desc()
+        _native.call('chr_daq_acquire_events', ctypes.byref(ph), len(gpuphotons.pos), bounds.ctypes.data, nevents,
+                     rng_states.gpudata, len(rng_states), 0x1 << 2, self.solid_id_map_gpu.gpudata,
+                     ctypes.byref(self._desc), t_int.gpudata, q_int.gpudata, hist.gpudata, q.gpudata,
+                     ctypes.c_float(weight), int(nthreads_per_block), int(max_blocks), current_stream())
+        return GPUEventChannels(t_int, q_int, hist, q, nevents, self.nchannels, host=self._event_host_words)

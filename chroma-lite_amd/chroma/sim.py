@@ -4,7 +4,9 @@ Batches events (never splitting one), uploads photons, propagates them on the
 device with the reference's launch shape (nthreads_per_block=512,
 max_blocks=1024 -> 524,288 RNG slots) and splits the detected hits back into
 events.  Photon tracking, GPU-resident inputs and the per-event DAQ
-(run_daq=True, chroma.gpu.daq) are supported as in the reference.
+(run_daq=True, chroma.gpu.daq) are supported as in the reference; the DAQ of a
+batch's events runs in groups of one native call each (Simulation.daq_events),
+with the per-event loop's results.
 """
 import os
 import time
@@ -40,6 +42,16 @@ def agree_seed(seed, group=None):
     return int(box.item())
 
 
+def daq_event_groups(bounds, nchannels, budget):
+    """The events of a batch (photon offsets `bounds`) in consecutive groups
+    [first, last) for GPUDaq.acquire_events: as many events per group as fit
+    `budget` bytes of channel rows (four 4-byte words per channel and event),
+    at least one.  Every event is in exactly one group, in order."""
+    nevents = len(bounds) - 1
+    per_group = max(1, int(budget) // (16 * int(nchannels)))
+    return [(first, min(first + per_group, nevents)) for first in range(0, nevents, per_group)]
+
+
 class _Batch(object):
     """One batch of events on the device: its GPUPhotons (uploaded when the
     batch closes, before a later batch can restamp a shared source's evidx),
@@ -60,6 +72,15 @@ class Simulation(object):
     # propagate per batch (tests/test_gpu_sim_pipeline.py).  1 = the reference's
     # one-batch-at-a-time loop (sim.py:116-160).
     pipeline_batches = 8
+    # run_daq: the DAQ of a batch's events in groups of one native call each
+    # (GPUDaq.acquire_events; channels and rng_states bit-identical to the
+    # per-event loop, tests/test_gpu_daq_events.py).  False = the reference's
+    # begin / acquire / end per event (sim.py:143-152).
+    daq_events = True
+    # bytes of channel rows (16 per channel and event) one group may hold on the
+    # device; a cap on device and pinned host memory (a batch of one-photon
+    # events on a large detector would otherwise ask for its product)
+    daq_group_bytes = 64 << 20
 
     def __init__(self, detector, seed=None, cuda_device=None, photon_tracking=False, nthreads_per_block=512,
                  max_blocks=1024):
@@ -127,15 +148,35 @@ class Simulation(object):
                              nthreads_per_block=self.nthreads_per_block, max_blocks=self.max_blocks)
         return self.gpu_daq.end_acquire().get()
 
+    def _acquire_events(self, b, bounds):
+        """DAQ of the consecutive events [bounds[e], bounds[e+1]) of the batch in
+        one call: their event.Channels in order, or None where the DAQ is not
+        batched (the caller then runs _acquire per event)."""
+        return self.gpu_daq.acquire_events(b.gpu_photons, self.rng_states, bounds,
+                                           nthreads_per_block=self.nthreads_per_block,
+                                           max_blocks=self.max_blocks).get()
+
     def _emit(self, b, keep_photons_beg=False, keep_photons_end=False, keep_hits=True, keep_flat_hits=True,
               run_daq=False):
-        """Split a propagated batch back into its events (sim.py:72-110)."""
+        """Split a propagated batch back into its events (sim.py:72-110).
+
+        With run_daq and daq_events the DAQ runs for a group of events at a time
+        (daq_event_groups under daq_group_bytes), each group just before its
+        first event is yielded, so its draws fall between the same propagates
+        as the per-event loop's.  A caller who abandons the generator inside a
+        batch leaves rng_states advanced to the end of the current group, not
+        of the current event."""
         if keep_photons_end:
             photons_end = self._photons_end(b)
         has_channels = hasattr(self.detector, 'num_channels')
         batch_hits = None
         if has_channels and (keep_hits or keep_flat_hits):
             batch_hits = self._batch_hits(b)
+        run_daq = run_daq and getattr(self, 'gpu_daq', None) is not None
+        groups = {}
+        if run_daq and self.daq_events:
+            groups = dict(daq_event_groups(b.bounds, self.gpu_daq.nchannels, self.daq_group_bytes))
+        group_first, group_channels = 0, None
         for i, (ev, (start, end)) in enumerate(zip(b.events, zip(b.bounds[:-1], b.bounds[1:]))):
             if not keep_photons_beg:
                 ev.photons_beg = None
@@ -159,8 +200,18 @@ class Simulation(object):
                     ev.hits = {int(ch): ev_hits[ev_hits.channel == ch] for ch in np.unique(ev_hits.channel)}
                 if keep_flat_hits:
                     ev.flat_hits = ev_hits
-            if run_daq and getattr(self, 'gpu_daq', None) is not None:
-                ev.channels = self._acquire(b, start, end)
+            if run_daq:
+                if i in groups:
+                    group_first, group_channels = i, None
+                    if groups[i] - i > 1:           # one event alone is quicker through _acquire (DESIGN)
+                        group_channels = self._acquire_events(b, b.bounds[i:groups[i] + 1])
+                        if group_channels is None:  # not batched: per event from here on
+                            groups = {}
+                if group_channels is not None:
+                    ev.channels = group_channels[i - group_first]
+                    group_channels[i - group_first] = None
+                else:
+                    ev.channels = self._acquire(b, start, end)
             yield ev
 
     def _simulate_batch(self, batch_events, keep_photons_beg=False, keep_photons_end=False, keep_hits=True,
@@ -351,6 +402,9 @@ class ShardedSimulation(Simulation):
             return shard.unpack_photons(shard.allgather_rows(rows, self.group))
         rows = shard.gather_rows(rows, 0, self.group)
         return shard.unpack_photons(rows) if rows is not None else None
+
+    def _acquire_events(self, b, bounds):
+        return None     # not batched: every event's channels are reduced across the ranks (_acquire)
 
     def _acquire(self, b, start, end):
         from chroma.gpu import shard

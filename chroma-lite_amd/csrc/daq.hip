@@ -16,6 +16,7 @@
 
 #include <algorithm>
 #include <cstdint>
+#include <cstdlib>
 
 #include "../../include/chroma_amd.h"
 #include "../../include/chroma_fmath.h"
@@ -69,6 +70,22 @@ __global__ __launch_bounds__(BLOCK) void begin_kernel(uint32_t *time_int, uint32
     hist[i] = 0u;
 }
 
+// daq.cu:61-76: the draws for one detected photon on a channel (one uniform, two more
+// when accepted) and the three atomics on that channel's words
+__device__ __forceinline__ void draw_hit(chr_xorwow &rng, const DaqPhotons &ph, uint32_t photon_id, uint32_t history,
+                                         const chr_daq_detector &det, float global_weight, uint32_t *time_word,
+                                         uint32_t *q_word, uint32_t *hist_word) {
+    const float weight = ph.weights[photon_id] * global_weight;
+    if (chr_uniform01(&rng) < weight) {
+        const float time = ph.t[photon_id] + sample_cdf_xy(rng, det.time_cdf_len, det.d_time_cdf_x, det.d_time_cdf_y);
+        const float charge = sample_cdf_xy(rng, det.charge_cdf_len, det.d_charge_cdf_x, det.d_charge_cdf_y);
+        const uint32_t charge_int = chr_sat_u32(__builtin_roundf(charge / det.charge_unit));
+        atomicMin(time_word, __float_as_uint(time));
+        atomicAdd(q_word, charge_int);
+        atomicOr(hist_word, history);
+    }
+}
+
 // daq.cu:35-83 over all chunks of [start, start+n): slot loops over chunk positions
 __global__ __launch_bounds__(BLOCK) void run_daq_kernel(uint32_t *rng_states, uint32_t nslots, uint32_t detection_state,
                                                         int32_t start, uint32_t n, uint32_t cap, DaqPhotons ph,
@@ -88,17 +105,133 @@ __global__ __launch_bounds__(BLOCK) void run_daq_kernel(uint32_t *rng_states, ui
         const int channel_index = det.d_solid_id_to_channel_index[solid_id];
         if (!(channel_index >= 0 && (history & detection_state))) continue;
         if (!loaded) { load_rng(rng_states, nslots, slot, rng); loaded = true; }
-        const float weight = ph.weights[photon_id] * global_weight;
-        if (chr_uniform01(&rng) < weight) {
-            const float time = ph.t[photon_id] + sample_cdf_xy(rng, det.time_cdf_len, det.d_time_cdf_x, det.d_time_cdf_y);
-            const float charge = sample_cdf_xy(rng, det.charge_cdf_len, det.d_charge_cdf_x, det.d_charge_cdf_y);
-            const uint32_t charge_int = chr_sat_u32(__builtin_roundf(charge / det.charge_unit));
-            atomicMin(time_int + channel_index, __float_as_uint(time));
-            atomicAdd(q_int + channel_index, charge_int);
-            atomicOr(hist + channel_index, history);
+        draw_hit(rng, ph, photon_id, history, det, global_weight, time_int + channel_index, q_int + channel_index,
+                 hist + channel_index);
+    }
+    if (loaded) store_rng(rng_states, nslots, slot, rng);
+}
+
+// ---- every event of a batch in one launch (chr_daq_acquire_events)
+
+// The channel of photon p where run_daq_kernel would draw for it, else -1 (daq.cu:52-59).
+// A channel index beyond the detector's channels, which run_daq_kernel would write through,
+// counts as "not detected" here: it would land in another event's row.
+__device__ __forceinline__ int candidate_channel(const DaqPhotons &ph, uint32_t p, const uint32_t *solid_map,
+                                                 const chr_daq_detector &det, uint32_t detection_state) {
+    const int triangle_id = ph.last_hit[p];
+    if (triangle_id <= -1) return -1;
+    const int channel_index = det.d_solid_id_to_channel_index[(int)solid_map[triangle_id]];
+    if (channel_index < 0 || channel_index >= det.nchannels || !(ph.flags[p] & detection_state)) return -1;
+    return channel_index;
+}
+
+// shape (b), pass 1: candidate_channel of photons [first, first+n), one work-item each
+__global__ __launch_bounds__(BLOCK) void candidates_kernel(DaqPhotons ph, uint32_t first, uint32_t n,
+                                                           const uint32_t *solid_map, chr_daq_detector det,
+                                                           uint32_t detection_state, int32_t *cand) {
+    const uint32_t i = blockIdx.x * BLOCK + threadIdx.x;
+    if (i >= n) return;
+    cand[i] = candidate_channel(ph, first + i, solid_map, det, detection_state);
+}
+
+// The draws of run_daq_kernel for events e = 0 .. nevents-1 over photons
+// [bounds[e], bounds[e+1]), into row e of the accumulators.  The work-item is the RNG
+// slot: it takes part in event e iff slot < min(cap, n_e), visits positions slot,
+// slot+cap, ... there, and carries its state in registers from event to event (the
+// per-event launches' draw order).  The event loop and its skip are wave-uniform
+// (bounds through uniform loads, the wave's first slot in an SGPR).  Only the RNG
+// chain is serial across events: the candidate word of the slot's first position
+// (CAND: read from pass 1's array, shape (b); else computed through last_hit ->
+// solid_map -> channel, shape (a)) is read one event ahead of the draws.
+template <bool CAND>
+__global__ __launch_bounds__(BLOCK) void run_daq_events_kernel(uint32_t *rng_states, uint32_t nslots,
+                                                               uint32_t detection_state,
+                                                               const uint32_t *__restrict__ bounds, uint32_t nevents,
+                                                               uint32_t cap, DaqPhotons ph, const uint32_t *solid_map,
+                                                               chr_daq_detector det, const int32_t *__restrict__ cand,
+                                                               uint32_t *time_int, uint32_t *q_int, uint32_t *hist,
+                                                               float global_weight) {
+    const uint32_t slot = blockIdx.x * BLOCK + threadIdx.x;
+    const uint32_t wave_slot = __builtin_amdgcn_readfirstlane(slot);
+    const uint32_t first = bounds[0];
+    auto channel_of = [&](uint32_t p) -> int {
+        if (CAND) return cand[p - first];
+        return candidate_channel(ph, p, solid_map, det, detection_state);
+    };
+    auto head = [&](uint32_t e) -> int {
+        const uint32_t b0 = bounds[e], lim = min(cap, bounds[e + 1] - b0);
+        if (wave_slot >= lim) return -1;
+        return slot < lim ? channel_of(b0 + slot) : -1;
+    };
+    chr_xorwow rng;
+    bool loaded = false;
+    int next = head(0);
+    for (uint32_t e = 0; e < nevents; ++e) {
+        int channel_index = next;
+        if (e + 1 < nevents) next = head(e + 1);
+        const uint32_t b0 = bounds[e], n = bounds[e + 1] - b0, lim = min(cap, n);
+        if (wave_slot >= lim) continue;
+        if (slot >= lim) continue;
+        const size_t row = (size_t)e * (uint32_t)det.nchannels;
+        for (uint32_t pos = slot; pos < n; pos += cap) {
+            if (pos != slot) channel_index = channel_of(b0 + pos);
+            if (channel_index < 0) continue;
+            if (!loaded) { load_rng(rng_states, nslots, slot, rng); loaded = true; }
+            const size_t w = row + (uint32_t)channel_index;
+            draw_hit(rng, ph, b0 + pos, ph.flags[b0 + pos], det, global_weight, time_int + w, q_int + w, hist + w);
         }
     }
     if (loaded) store_rng(rng_states, nslots, slot, rng);
+}
+
+// convert_charge_int_to_float (daq.cu:164-172) over every row
+__global__ __launch_bounds__(BLOCK) void convert_charge_kernel(const uint32_t *q_int, float *q, uint32_t n,
+                                                               float charge_unit) {
+    const uint32_t i = blockIdx.x * BLOCK + threadIdx.x;
+    if (i < n) q[i] = (float)q_int[i] * charge_unit;
+}
+
+// Device and pinned host words for the event bounds, and the candidate words of shape (b)
+// (per host thread and device, grown on demand).
+struct EventBuffers {
+    uint32_t *d_bounds = nullptr, *h_bounds = nullptr;
+    int32_t *d_cand = nullptr;
+    size_t nbounds = 0, ncand = 0;
+};
+
+int event_buffers(size_t nbounds, size_t ncand, EventBuffers **out) {
+    static thread_local EventBuffers s[16];
+    int dev = 0;
+    CHR_HIP_CHECK(hipGetDevice(&dev));
+    EventBuffers &x = s[dev & 15];
+    if (x.nbounds < nbounds) {
+        if (x.d_bounds) CHR_HIP_CHECK(hipFree(x.d_bounds));
+        x.d_bounds = nullptr;
+        if (x.h_bounds) CHR_HIP_CHECK(hipHostFree(x.h_bounds));
+        x.h_bounds = nullptr;
+        x.nbounds = 0;
+        const size_t grown = nbounds + nbounds / 2;
+        CHR_HIP_CHECK(hipMalloc((void **)&x.d_bounds, grown * 4));
+        CHR_HIP_CHECK(hipHostMalloc((void **)&x.h_bounds, grown * 4, hipHostMallocDefault));
+        x.nbounds = grown;
+    }
+    if (x.ncand < ncand) {
+        if (x.d_cand) CHR_HIP_CHECK(hipFree(x.d_cand));
+        x.d_cand = nullptr;
+        x.ncand = 0;
+        const size_t grown = ncand + ncand / 2;
+        CHR_HIP_CHECK(hipMalloc((void **)&x.d_cand, grown * 4));
+        x.ncand = grown;
+    }
+    *out = &x;
+    return CHR_OK;
+}
+
+// CHR_DAQ_EVENTS_SHAPE=a: one kernel that computes each event's candidate word one event
+// ahead of the draws (A/B; default b: the parallel candidate pass, then the draws)
+static bool events_candidate_pass() {
+    const char *e = getenv("CHR_DAQ_EVENTS_SHAPE");
+    return !(e && e[0] == 'a');
 }
 
 // daq.cu:85-145: one photon per workgroup of `ntpb` slots; workgroup b runs
@@ -243,6 +376,78 @@ extern "C" int chr_daq_end(const uint32_t *d_time_int, float *d_time, const uint
                        d_q, n, nchannels, charge_unit);
     CHR_HIP_CHECK(hipGetLastError());
     CHR_HIP_CHECK(hipStreamSynchronize((hipStream_t)stream));
+    return CHR_OK;
+}
+
+extern "C" int chr_daq_acquire_events(const chr_photons *ph, int32_t nphotons, const int64_t *h_bounds,
+                                      int32_t nevents, uint32_t *d_rng_states, uint32_t rng_nslots,
+                                      uint32_t detection_state, const uint32_t *d_solid_map,
+                                      const chr_daq_detector *det, uint32_t *d_time_int, uint32_t *d_q_int,
+                                      uint32_t *d_history, float *d_q, float global_weight, int32_t ntpb,
+                                      int32_t max_blocks, void *vstream) {
+    if (!ph || !ph->d_t || !ph->d_flags || !ph->d_last_hit_triangles || !ph->d_weights || !h_bounds ||
+        !d_rng_states || !d_solid_map || !det || !det->d_solid_id_to_channel_index || !d_time_int || !d_q_int ||
+        !d_history || !d_q)
+        return chr::fail(CHR_ERR_INVALID, "chr_daq_acquire_events: null argument");
+    if (!det->d_time_cdf_x || !det->d_time_cdf_y || !det->d_charge_cdf_x || !det->d_charge_cdf_y ||
+        det->time_cdf_len < 2 || det->charge_cdf_len < 2)
+        return chr::fail(CHR_ERR_INVALID, "chr_daq_acquire_events: time/charge CDFs missing");
+    if (nevents < 0 || nphotons < 0 || ntpb <= 0 || max_blocks <= 0 || det->nchannels <= 0)
+        return chr::fail(CHR_ERR_INVALID, "chr_daq_acquire_events: bad event count / launch shape / channel count");
+    if (h_bounds[0] < 0 || h_bounds[nevents] > nphotons)
+        return chr::fail(CHR_ERR_INVALID, "chr_daq_acquire_events: bounds [%lld, %lld] outside the %d photons",
+                         (long long)h_bounds[0], (long long)h_bounds[nevents], nphotons);
+    int64_t max_n = 0;
+    for (int32_t e = 0; e < nevents; ++e) {
+        if (h_bounds[e + 1] < h_bounds[e])
+            return chr::fail(CHR_ERR_INVALID, "chr_daq_acquire_events: bounds decrease at event %d", e);
+        max_n = std::max(max_n, h_bounds[e + 1] - h_bounds[e]);
+    }
+    // positions stay below 2^31, so a larger cap visits the same ones (and pos + cap cannot wrap)
+    const uint32_t cap = (uint32_t)std::min<uint64_t>((uint64_t)ntpb * max_blocks, 0x80000000u);
+    const uint32_t threads = (uint32_t)std::min<int64_t>(cap, max_n);
+    if (threads > rng_nslots)
+        return chr::fail(CHR_ERR_INVALID, "chr_daq_acquire_events: %u photons per chunk but only %u rng states",
+                         threads, rng_nslots);
+    const uint64_t words = (uint64_t)nevents * (uint32_t)det->nchannels;
+    if (words > 0x80000000u)
+        return chr::fail(CHR_ERR_INVALID, "chr_daq_acquire_events: %d events of %d channels exceed 2^31 words",
+                         nevents, det->nchannels);
+    if (nevents == 0) return CHR_OK;
+
+    hipStream_t stream = (hipStream_t)vstream;
+    hipLaunchKernelGGL(begin_kernel, dim3(grid_for(words)), dim3(BLOCK), 0, stream, d_time_int, d_q_int, d_history,
+                       (uint32_t)words, __builtin_bit_cast(uint32_t, 1e9f));
+    CHR_HIP_CHECK(hipGetLastError());
+    if (threads > 0) {
+        const bool pass = events_candidate_pass();
+        const uint32_t first = (uint32_t)h_bounds[0], span = (uint32_t)(h_bounds[nevents] - h_bounds[0]);
+        EventBuffers *buf = nullptr;
+        CHR_TRY(event_buffers((size_t)nevents + 1, pass ? span : 0, &buf));
+        for (int32_t e = 0; e <= nevents; ++e) buf->h_bounds[e] = (uint32_t)h_bounds[e];
+        CHR_HIP_CHECK(hipMemcpyAsync(buf->d_bounds, buf->h_bounds, ((size_t)nevents + 1) * 4, hipMemcpyHostToDevice,
+                                     stream));
+        DaqPhotons p{ph->d_t, ph->d_weights, ph->d_flags, ph->d_last_hit_triangles};
+        if (pass) {
+            hipLaunchKernelGGL(candidates_kernel, dim3(grid_for(span)), dim3(BLOCK), 0, stream, p, first, span,
+                               d_solid_map, *det, detection_state, buf->d_cand);
+            CHR_HIP_CHECK(hipGetLastError());
+            hipLaunchKernelGGL(run_daq_events_kernel<true>, dim3(grid_for(threads)), dim3(BLOCK), 0, stream,
+                               d_rng_states, rng_nslots, detection_state, buf->d_bounds, (uint32_t)nevents, cap, p,
+                               d_solid_map, *det, buf->d_cand, d_time_int, d_q_int, d_history, global_weight);
+        } else {
+            hipLaunchKernelGGL(run_daq_events_kernel<false>, dim3(grid_for(threads)), dim3(BLOCK), 0, stream,
+                               d_rng_states, rng_nslots, detection_state, buf->d_bounds, (uint32_t)nevents, cap, p,
+                               d_solid_map, *det, (const int32_t *)nullptr, d_time_int, d_q_int, d_history,
+                               global_weight);
+        }
+        CHR_HIP_CHECK(hipGetLastError());
+    }
+    hipLaunchKernelGGL(convert_charge_kernel, dim3(grid_for(words)), dim3(BLOCK), 0, stream, d_q_int, d_q,
+                       (uint32_t)words, det->charge_unit);
+    CHR_HIP_CHECK(hipGetLastError());
+    // the pinned bounds are rewritten by the next call, and GPUDaq.acquire synchronises too (daq.py:91)
+    CHR_HIP_CHECK(hipStreamSynchronize(stream));
     return CHR_OK;
 }
 

@@ -478,6 +478,29 @@ int chr_daq_acquire(const chr_photons *ph, uint32_t *d_rng_states, uint32_t rng_
 int chr_daq_end(const uint32_t *d_time_int, float *d_time, const uint32_t *d_q_int, float *d_q, uint32_t n,
                 int32_t nchannels, float charge_unit, void *stream);
 
+/* replaces: the per-event DAQ loop, GPUDaq.begin_acquire / acquire / end_acquire
+ * (gpu/daq.py:56-101) as driven once per event by sim.py:143-152.  ndaq = 1 DAQ
+ * passes for the nevents consecutive photon ranges [h_bounds[e], h_bounds[e+1])
+ * of one chr_photons (h_bounds: nevents+1 non-decreasing host offsets within
+ * [0, nphotons]), in a number of launches that does not depend on nevents.
+ * Outputs are nevents rows of det->nchannels words, row e = event e: d_time_int
+ * (the f32 earliest times' bit patterns, 1e9 where nothing was recorded),
+ * d_q_int, d_history, and d_q = d_q_int * charge_unit in EVERY row (each row is
+ * its own ndaq = 1 acquisition).  Rows and the RNG slot states afterwards are
+ * bit-identical to chr_daq_begin(1e9) + chr_daq_acquire(start = h_bounds[e],
+ * n = h_bounds[e+1] - h_bounds[e], ndaq = 1) + chr_daq_end for e = 0, 1, ...:
+ * with cap = nthreads_per_block*max_blocks, slot s draws in event e iff
+ * s < min(cap, n_e), for positions s, s+cap, ... of it, events ascending.
+ * CHR_ERR_INVALID before any launch for null arguments, missing CDFs, nevents
+ * < 0, h_bounds decreasing / below 0 / beyond nphotons, min(cap, max n_e) >
+ * rng_nslots, or nevents*nchannels > 2^31; nevents == 0 is CHR_OK and touches
+ * nothing.  Synchronous. */
+int chr_daq_acquire_events(const chr_photons *ph, int32_t nphotons, const int64_t *h_bounds, int32_t nevents,
+                           uint32_t *d_rng_states, uint32_t rng_nslots, uint32_t detection_state,
+                           const uint32_t *d_solid_map, const chr_daq_detector *det,
+                           uint32_t *d_time_int, uint32_t *d_q_int, uint32_t *d_history, float *d_q,
+                           float global_weight, int32_t nthreads_per_block, int32_t max_blocks, void *stream);
+
 /* Detected photons per channel, ACCUMULATED into d_counts[nchannels] (u32; the
  * caller zeroes it): the selection of count_photon_hits (propagate.cu:172-199)
  * histogrammed by channel.  No reference counterpart -- it is the per-rank
