@@ -142,6 +142,7 @@ class Event(object):
         self.photons_beg = photons_beg
         self.photons_end = photons_end
         self.photon_tracks = photon_tracks
+        self.photon_tracks_flat = None      # (offsets, Photons) of the same tracks back to back (Simulation)
         self.photon_parent_trackids = photon_parent_trackids
         self.hits = hits
         self.flat_hits = flat_hits

@@ -110,6 +110,15 @@ _SIGNATURES = {
                               c_i32, c_i32, c_i32, ctypes.POINTER(PropagateStats), c_vp]),
     'chr_propagate_batches': (c_i32, [c_vp, ctypes.POINTER(PhotonsDesc), c_vp, c_vp, c_vp, c_u32, c_vp, c_u32, c_i32,
                                       c_i32, c_i32, c_i32, c_i32, ctypes.POINTER(PropagateStats), c_vp]),
+    'chr_propagate_tracked': (c_i32, [c_vp, ctypes.POINTER(PhotonsDesc), c_u32, c_u32, c_u32, c_vp, c_u32, c_i32, c_i32,
+                                      c_i32, c_i32, c_i32, c_u64, ctypes.POINTER(c_vp), ctypes.POINTER(PropagateStats),
+                                      c_vp]),
+    'chr_tracks_info': (c_i32, [c_vp, ctypes.POINTER(c_u32), ctypes.POINTER(c_u64), ctypes.POINTER(c_u32)]),
+    'chr_tracks_entry_counts': (c_i32, [c_vp, c_vp]),
+    'chr_tracks_device': (c_i32, [c_vp, c_i32, ctypes.POINTER(c_vp), ctypes.POINTER(c_vp)]),
+    'chr_tracks_copy': (c_i32, [c_vp, c_i32, c_vp, c_vp]),
+    'chr_tracks_free': (c_i32, [c_vp]),
+    'chr_tracks_unpack': (c_i32, [c_vp, c_u64, c_vp, c_u32, ctypes.POINTER(PhotonsDesc), c_vp]),
     'chr_photon_hits': (c_i32, [ctypes.POINTER(PhotonsDesc), c_i32, c_i32, c_u32, c_vp, c_vp,
                                 ctypes.POINTER(PhotonsDesc), c_vp, ctypes.POINTER(c_u32), c_vp]),
     'chr_select_photons': (c_i32, [ctypes.POINTER(PhotonsDesc), c_i32, c_i32, c_u32, ctypes.POINTER(PhotonsDesc),

@@ -3,7 +3,9 @@
 Same constructor, attributes (pos dir pol wavelengths t last_hit_triangles
 flags weights evidx true_nphotons ncopies) and methods; device work goes
 through the C ABI (libchroma_amd.so): chr_propagate for the whole host step
-loop of photon.py:226-293, chr_propagate_chunk when tracking, chr_photon_hits
+loop of photon.py:226-293, chr_propagate_tracked when tracking (the tracks are
+recorded on the device, chroma.gpu.tracks; chr_propagate_chunk driven from here
+with device_tracking cleared), chr_photon_hits
 (count_photon_hits/copy_photon_hits), chr_select_photons (count_photons/
 copy_photons), chr_copy_photon_queue and chr_photon_duplicate.
 
@@ -57,6 +59,13 @@ def _resolve_nphotons(ph):
 
 
 class GPUPhotons(object):
+    # propagate(track=True): the tracks are recorded on the device by one native call
+    # (propagate_tracks, chr_propagate_tracked) and downloaded once; photons, rng_states
+    # and the returned entries are word-identical to the host-driven loop
+    # (tests/test_gpu_photon_tracks.py).  False = that loop (_propagate_tracked): one
+    # chunk launch, nine gathers and ten downloads per step (photon.py:252-293).
+    device_tracking = True
+
     def __init__(self, photons, ncopies=1, copy_flags=True, copy_triangles=True, copy_weights=True):
         nphotons = _resolve_nphotons(photons)
         total = nphotons * ncopies
@@ -182,8 +191,35 @@ class GPUPhotons(object):
                 print('WARNING: %d BVH traversals exceeded the 1000-entry stack' % stats.stack_overflows,
                       file=sys.stderr)
             return None
+        if self.device_tracking:
+            with self.propagate_tracks(gpu_geometry, rng_states, nthreads_per_block, max_blocks, max_steps,
+                                       use_weights, scatter_first) as tracks:
+                return tracks.steps()
         return self._propagate_tracked(gpu_geometry, rng_states, nthreads_per_block, max_blocks, max_steps,
                                        use_weights, scatter_first)
+
+    def propagate_tracks(self, gpu_geometry, rng_states, nthreads_per_block=256, max_blocks=1024, max_steps=10,
+                         use_weights=False, scatter_first=0, capacity_hint=0):
+        """propagate(track=True) with the tracks left on the device: returns a
+        chroma.gpu.tracks.PhotonTracks (steps(), flat(), track(i), device(order)).
+        capacity_hint: records (64 B each) to allocate at first, 0 for two
+        entries' worth; the buffer grows geometrically from there."""
+        from chroma.gpu.tracks import PhotonTracks
+        nslots = len(rng_states)
+        if nthreads_per_block * max_blocks > nslots:
+            raise ValueError('rng_states must have at least nthreads_per_block*max_blocks states')
+        stats = _native.PropagateStats()
+        handle = ctypes.c_void_p()
+        _native.call('chr_propagate_tracked', ctypes.c_void_p(gpu_geometry.gpudata), ctypes.byref(self._desc()),
+                     self.pos.size, self.true_nphotons, self.ncopies, rng_states.gpudata, nslots, nthreads_per_block,
+                     max_blocks, max_steps, int(bool(use_weights)), int(scatter_first), int(capacity_hint),
+                     ctypes.byref(handle), ctypes.byref(stats), current_stream())
+        tracks = PhotonTracks(handle, self.evidx)
+        tracks.last_stats = self.last_stats = stats
+        if stats.stack_overflows:
+            print('WARNING: %d BVH traversals exceeded the 1000-entry stack' % stats.stack_overflows,
+                  file=sys.stderr)
+        return tracks
 
     def _propagate_tracked(self, gpu_geometry, rng_states, ntpb, max_blocks, max_steps, use_weights,
                            scatter_first):

@@ -52,6 +52,20 @@ def daq_event_groups(bounds, nchannels, budget):
     return [(first, min(first + per_group, nevents)) for first in range(0, nevents, per_group)]
 
 
+def _event_tracks_flat(flat, start, end):
+    """(offsets, Photons) of the photons [start, end) of a batch's photon-major
+    tracks (PhotonTracks.flat()): the event's own offsets, from 0."""
+    offsets, photons = flat
+    lo, hi = int(offsets[start]), int(offsets[end])
+    return offsets[start:end + 1] - lo, photons[lo:hi]
+
+
+def _track_list(offsets, photons):
+    """One event.Photons per photon: the slices of `photons` between consecutive
+    offsets (an empty Photons() for a photon that was never queued)."""
+    return [photons[a:b] if b > a else event.Photons() for a, b in zip(offsets[:-1].tolist(), offsets[1:].tolist())]
+
+
 class _Batch(object):
     """One batch of events on the device: its GPUPhotons (uploaded when the
     batch closes, before a later batch can restamp a shared source's evidx),
@@ -81,6 +95,10 @@ class Simulation(object):
     # device; a cap on device and pinned host memory (a batch of one-photon
     # events on a large detector would otherwise ask for its product)
     daq_group_bytes = 64 << 20
+    # photon_tracking: build ev.photon_tracks, one event.Photons per photon (the
+    # reference's list).  False leaves it None for callers who read only
+    # ev.photon_tracks_flat = (offsets, Photons), the same records back to back.
+    photon_track_lists = True
 
     def __init__(self, detector, seed=None, cuda_device=None, photon_tracking=False, nthreads_per_block=512,
                  max_blocks=1024):
@@ -131,7 +149,12 @@ class Simulation(object):
             gpu.propagate_batches([b.gpu_photons for b in live], self.gpu_geometry, self.rng_states, **kw)
             return 1
         for b in live:
-            b.tracking = b.gpu_photons.propagate(self.gpu_geometry, self.rng_states, track=self.photon_tracking, **kw)
+            if self.photon_tracking and b.gpu_photons.device_tracking:
+                # the tracks stay on the device until _emit downloads them once, photon-major
+                b.tracking = b.gpu_photons.propagate_tracks(self.gpu_geometry, self.rng_states, **kw)
+            else:
+                b.tracking = b.gpu_photons.propagate(self.gpu_geometry, self.rng_states, track=self.photon_tracking,
+                                                     **kw)
         return 0
 
     def _batch_hits(self, b):
@@ -177,10 +200,18 @@ class Simulation(object):
         if run_daq and self.daq_events:
             groups = dict(daq_event_groups(b.bounds, self.gpu_daq.nchannels, self.daq_group_bytes))
         group_first, group_channels = 0, None
+        flat = None
+        if self.photon_tracking and isinstance(b.tracking, gpu.PhotonTracks):
+            flat = b.tracking.flat()      # one download of the batch's records, photon-major
+            b.tracking.close()
         for i, (ev, (start, end)) in enumerate(zip(b.events, zip(b.bounds[:-1], b.bounds[1:]))):
             if not keep_photons_beg:
                 ev.photons_beg = None
-            if self.photon_tracking:
+            if flat is not None:
+                ev.photon_tracks_flat = _event_tracks_flat(flat, int(start), int(end))
+                if self.photon_track_lists:
+                    ev.photon_tracks = _track_list(*ev.photon_tracks_flat)
+            elif self.photon_tracking:
                 step_ids, step_photons = b.tracking
                 tracks = [[] for _ in range(end - start)]
                 for ids, photons in zip(step_ids, step_photons):

@@ -25,6 +25,8 @@
 #include <cstdlib>
 #include <cstring>
 #include <functional>
+#include <memory>
+#include <new>
 #include <type_traits>
 #include <vector>
 
@@ -36,6 +38,7 @@
 #include "device_math.h"
 #include "sampling.h"
 #include "slab_plane.h"
+#include "tracks.h"
 #include "wide_bvh.h"
 
 namespace chr {
@@ -5417,6 +5420,218 @@ extern "C" int chr_propagate(const chr_geometry *g, const chr_photons *ph, uint3
     st.trace_ms += trace_ms;
     st.final_alive = (step < max_steps) ? (uint32_t)n : 0u;
     if (stats) *stats = st;
+    return CHR_OK;
+}
+
+// ---------------------------------------------------------------- photon tracks
+// device words of one tracked propagate besides the handle's: freed on every way out
+struct TrackTemp {
+    uint32_t *len = nullptr;   // [nphotons + 1] track lengths (the last word stays 0), then [1] the bad-id count
+    ~TrackTemp() { if (len) (void)hipFree(len); }
+};
+
+// room for `need` records in the step-major buffer: a new allocation of at least twice
+// the old and a device-to-device copy of the `used` records on the stream
+static int tracks_reserve(chr_tracks &t, uint64_t used, uint64_t need, hipStream_t stream) {
+    if (need <= t.capacity) return CHR_OK;
+    const uint64_t cap = std::max<uint64_t>(need, 2 * t.capacity);
+    uint4 *p = nullptr;
+    if (hipMalloc((void **)&p, (size_t)cap * CHR_TRACK_WORDS * 4) != hipSuccess) {
+        (void)hipGetLastError();
+        return chr::fail(CHR_ERR_NOMEM, "chr_propagate_tracked: no memory for %llu track records",
+                         (unsigned long long)cap);
+    }
+    if (used) {
+        const hipError_t e = hipMemcpyAsync(p, t.d_step, (size_t)used * CHR_TRACK_WORDS * 4, hipMemcpyDeviceToDevice,
+                                            stream);
+        if (e != hipSuccess) {
+            (void)hipFree(p);
+            return chr::fail(CHR_ERR_HIP, "chr_propagate_tracked: copying the track records: %s", hipGetErrorString(e));
+        }
+    }
+    if (t.d_step) CHR_HIP_CHECK(hipFree(t.d_step));   // waits for the copy
+    t.d_step = p;
+    t.capacity = cap;
+    return CHR_OK;
+}
+
+// replaces: GPUPhotons.propagate(track=True) (chroma/gpu/photon.py:252-293): chr_propagate's
+// host loop with nsteps = 1 on every step, and one record per queued photon per entry
+// (tracks.hip) instead of the copy_queue gather and the downloads.  use_weights: the
+// shade kernel and the chunk kernel both take it with one step per launch and draw from
+// the photon's chunk slot, so it runs on whichever path the slot count selects, as
+// every other case does.
+extern "C" int chr_propagate_tracked(const chr_geometry *g, const chr_photons *ph, uint32_t nphotons,
+                                     uint32_t true_nphotons, uint32_t ncopies, uint32_t *d_rng_states,
+                                     uint32_t rng_nslots, int32_t ntpb, int32_t max_blocks, int32_t max_steps,
+                                     int32_t use_weights, int32_t scatter_first, uint64_t capacity_hint,
+                                     chr_tracks **out, chr_propagate_stats *stats, void *vstream) {
+    if (!out) return chr::fail(CHR_ERR_INVALID, "chr_propagate_tracked: null argument (out)");
+    *out = nullptr;
+    // arrays of no photons have no address (an empty allocation's pointer is NULL) and nothing
+    // is read through them: the other arguments are checked with a stand-in descriptor
+    static float none_f;
+    static uint32_t none_u;
+    static int32_t none_i;
+    const chr_photons none{&none_f, &none_f, &none_f, &none_f, &none_f, &none_f, &none_u, &none_i, &none_u};
+    CHR_TRY(check_propagate_args("chr_propagate_tracked", g, (nphotons == 0 && ph) ? &none : ph, nphotons,
+                                 true_nphotons, ncopies, d_rng_states, rng_nslots, ntpb, max_blocks, max_steps));
+    chr_propagate_stats st{};
+    std::unique_ptr<chr_tracks> tr(new (std::nothrow) chr_tracks());
+    if (!tr) return chr::fail(CHR_ERR_NOMEM, "chr_propagate_tracked: no memory for the handle");
+    tr->nphotons = nphotons;
+    tr->counts.push_back(nphotons);   // entry 0: the first queue
+    if (nphotons == 0) {              // an empty handle: nothing is launched
+        if (stats) *stats = st;
+        *out = tr.release();
+        return CHR_OK;
+    }
+    CHR_HIP_CHECK(hipGetDevice(&tr->device));
+    if (walks_reference_bvh(g)) CHR_TRY(chr::geometry_ref_nodes(g));
+    hipStream_t stream = (hipStream_t)vstream;
+    PropBufs b;
+    int rc = prop_bufs(nphotons, ntpb, max_blocks, 0, false, b);
+    if (rc) return rc;
+    const uint64_t cap = b.cap;
+    const uint32_t chunk_cap = (uint32_t)std::min<uint64_t>(cap, nphotons);
+    const bool fused = b.fused;
+    uint32_t *const *q = b.q;
+    uint32_t *pinned = b.pinned;
+    FlatCtx &fc = b.fc;
+    TrackTemp tmp;
+    if (hipMalloc((void **)&tmp.len, ((size_t)nphotons + 2) * 4) != hipSuccess) {
+        (void)hipGetLastError();
+        return chr::fail(CHR_ERR_NOMEM, "chr_propagate_tracked: no memory for %u track lengths", nphotons);
+    }
+    uint32_t *bad = tmp.len + (size_t)nphotons + 1;
+    CHR_HIP_CHECK(hipMemsetAsync(tmp.len, 0, ((size_t)nphotons + 2) * 4, stream));
+    const uint64_t first_cap = capacity_hint ? capacity_hint : (uint64_t)nphotons * (max_steps >= 1 ? 2u : 1u);
+    if ((rc = tracks_reserve(*tr, 0, std::max<uint64_t>(first_cap, nphotons), stream))) return rc;
+    if ((rc = prop_start(b, nphotons, true_nphotons, ncopies, stream))) return rc;
+    fc.enrol_next = fused;
+    // entry 0: the input state of the first queue
+    if ((rc = chr::tracks_record(ph, q[0] + 1, nphotons, nphotons, 0u, tr->d_step, tmp.len, bad, stream))) return rc;
+    uint64_t nrec = nphotons;
+    const size_t max_chunks = fused ? 2 : (nphotons + chunk_cap - 1) / chunk_cap;   // fused: step + its walk
+    std::vector<hipEvent_t> *evp = nullptr;
+    if ((rc = timing_events(2 * max_chunks, &evp))) return rc;
+    std::vector<hipEvent_t> &events = *evp;
+    double kernel_ms = 0.0, trace_ms = 0.0;
+    bool split_step = false;
+    int64_t n_launch = 0;
+    auto collect = [&](size_t nchunks) -> int {
+        for (size_t c = 0; c < nchunks; ++c) {
+            float ms = 0.0f;
+            CHR_HIP_CHECK(hipEventElapsedTime(&ms, events[2 * c], events[2 * c + 1]));
+            kernel_ms += ms;
+        }
+        if (fused && split_step) {
+            float ms = 0.0f;
+            CHR_HIP_CHECK(hipEventElapsedTime(&ms, events[2], events[3]));
+            trace_ms += ms;
+            if (st.trace_ms_n < CHR_TRACE_MS_MAX) {
+                st.trace_launch_rays[st.trace_ms_n] = (uint32_t)n_launch;
+                st.trace_launch_ms[st.trace_ms_n++] = ms;
+            }
+        }
+        return CHR_OK;
+    };
+    int cur = 0;
+    int64_t n = nphotons;
+    int step = 0;
+    size_t nchunks = 0;
+    while (step < max_steps) {
+        n_launch = n;
+        nchunks = 0;
+        if (fused) {
+            rc = launch_step(g, ph, d_rng_states, rng_nslots, (uint32_t)cap, (uint32_t)n, q[cur] + 1, q[cur ^ 1], 1,
+                             use_weights, scatter_first, b.scratch, stream, events[0], events[1], b.hits, b.sort_space,
+                             step == 0, events[2], events[3], &split_step, &fc);
+            if (rc) return rc;
+            st.launches++;
+            nchunks = 1;
+            if (split_step) {
+                st.trace_launches++;
+                st.trace_rays += (uint64_t)n;
+            }
+        } else {
+            int64_t first = 0;
+            while (first < n) {
+                // chunk_iterator (tools.py:159-180)
+                const int64_t left = n - first;
+                int64_t blocks = left / ntpb + (left % ntpb != 0);
+                if (blocks > max_blocks) blocks = max_blocks;
+                const int64_t count = std::min<int64_t>(left, blocks * ntpb);
+                rc = launch_chunk(g, ph, d_rng_states, rng_nslots, (int32_t)first, (int32_t)count, q[cur] + 1,
+                                  q[cur ^ 1], 1, use_weights, scatter_first, b.scratch, stream, events[2 * nchunks],
+                                  events[2 * nchunks + 1]);
+                if (rc) return rc;
+                st.launches++;
+                nchunks++;
+                first += count;
+            }
+        }
+        st.steps_run++;
+        step++;
+        scatter_first = 0;
+        // entry `step`: the step's input queue after its write-back (the host knows its length)
+        if ((rc = tracks_reserve(*tr, nrec, nrec + (uint64_t)n, stream))) return rc;
+        if ((rc = chr::tracks_record(ph, q[cur] + 1, (uint32_t)n, nphotons, (uint32_t)step, tr->d_step + 4 * nrec,
+                                     tmp.len, bad, stream)))
+            return rc;
+        tr->counts.push_back((uint64_t)n);
+        nrec += (uint64_t)n;
+        if (step < max_steps) {
+            cur ^= 1;
+            // read the survivor count (photon.py:284) and reset the other header
+            CHR_HIP_CHECK(hipMemcpyAsync(pinned, q[cur], 4, hipMemcpyDeviceToHost, stream));
+            CHR_HIP_CHECK(hipStreamSynchronize(stream));
+            st.host_syncs++;
+            if ((rc = collect(nchunks))) return rc;
+            nchunks = 0;
+            n = (int64_t)pinned[0] - 1;
+            if (n < 0 || n > (int64_t)nphotons)
+                return chr::fail(CHR_ERR_INTERNAL, "chr_propagate_tracked: queue header %u after step %d", pinned[0], step);
+            pinned[1] = 1;
+            CHR_HIP_CHECK(hipMemcpyAsync(q[cur ^ 1], pinned + 1, 4, hipMemcpyHostToDevice, stream));
+            if (n == 0) break;
+        }
+    }
+    // the two orders' offsets, and the photon-major copy
+    tr->nrecords = nrec;
+    const size_t nentries = tr->counts.size();
+    std::vector<uint64_t> soff(nentries + 1, 0);
+    for (size_t k = 0; k < nentries; ++k) soff[k + 1] = soff[k] + tr->counts[k];
+    if (hipMalloc((void **)&tr->d_step_offsets, (nentries + 1) * 8) != hipSuccess ||
+        hipMalloc((void **)&tr->d_flat_offsets, ((size_t)nphotons + 1) * 8) != hipSuccess ||
+        hipMalloc((void **)&tr->d_flat, (size_t)nrec * CHR_TRACK_WORDS * 4) != hipSuccess) {
+        (void)hipGetLastError();
+        return chr::fail(CHR_ERR_NOMEM, "chr_propagate_tracked: no memory for %llu photon-major track records",
+                         (unsigned long long)nrec);
+    }
+    CHR_HIP_CHECK(hipMemcpyAsync(tr->d_step_offsets, soff.data(), (nentries + 1) * 8, hipMemcpyHostToDevice, stream));
+    if ((rc = chr::tracks_offsets(tmp.len, nphotons, tr->d_flat_offsets, stream))) return rc;
+    if ((rc = chr::tracks_transpose(tr->d_step, nrec, tr->d_flat_offsets, nphotons, tr->d_flat, bad, stream))) return rc;
+    if ((rc = counter_readback(b, stream))) return rc;
+    CHR_HIP_CHECK(hipMemcpyAsync(pinned + 40, bad, 4, hipMemcpyDeviceToHost, stream));
+    CHR_HIP_CHECK(hipMemcpyAsync(pinned + 42, tr->d_flat_offsets + nphotons, 8, hipMemcpyDeviceToHost, stream));
+    CHR_HIP_CHECK(hipStreamSynchronize(stream));
+    st.host_syncs++;
+    if (nchunks && (rc = collect(nchunks))) return rc;
+    uint64_t total = 0;
+    std::memcpy(&total, pinned + 42, 8);
+    if (pinned[40] != 0)
+        return chr::fail(CHR_ERR_INTERNAL, "chr_propagate_tracked: %u queue words or records name no photon of the call",
+                         pinned[40]);
+    if (total != nrec)
+        return chr::fail(CHR_ERR_INTERNAL, "chr_propagate_tracked: track lengths sum to %llu, %llu records written",
+                         (unsigned long long)total, (unsigned long long)nrec);
+    counter_stats(st, b);
+    st.kernel_ms += kernel_ms;
+    st.trace_ms += trace_ms;
+    st.final_alive = max_steps == 0 ? nphotons : ((step < max_steps) ? (uint32_t)n : 0u);
+    if (stats) *stats = st;
+    *out = tr.release();
     return CHR_OK;
 }
 

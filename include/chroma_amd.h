@@ -32,7 +32,8 @@ enum chr_status {
     CHR_ERR_INVALID = 1,     /* bad argument (reference: ValueError / assert) */
     CHR_ERR_HIP = 2,         /* HIP runtime error (reference: pycuda LogicError/LaunchError) */
     CHR_ERR_NOMEM = 3,
-    CHR_ERR_STACK = 4        /* BVH stack overflow (reference: printf in mesh.h:111-114) */
+    CHR_ERR_STACK = 4,       /* BVH stack overflow (reference: printf in mesh.h:111-114) */
+    CHR_ERR_INTERNAL = 5     /* a device-side consistency check failed (no reference counterpart) */
 };
 
 /* photon history bits as stored on the device (reference photon.h:53-68).
@@ -323,6 +324,75 @@ int chr_propagate_batches(const chr_geometry *g, const chr_photons *phs, const u
                           int32_t nthreads_per_block, int32_t max_blocks, int32_t max_steps,
                           int32_t use_weights, int32_t scatter_first,
                           chr_propagate_stats *stats, void *stream);
+
+/* ---------------------------------------------------------- photon tracks
+ * replaces: GPUPhotons.propagate(track=True) (chroma/gpu/photon.py:252-293): the
+ * host step loop with every step a single step, the copy_queue gather and the
+ * per-step downloads of step_photon_ids / step_photons.  The tracks stay on the
+ * device behind an opaque handle that owns its memory, in two orders.
+ *
+ * Track record: CHR_TRACK_WORDS u32 words, 64-byte aligned --
+ *   [0] photon id   [1] history (the u32 the flags array holds)
+ *   [2..4] pos   [5..7] dir   [8..10] pol   [11] wavelength   [12] t   [13] weight
+ *   [14] last-hit triangle (i32)   [15] entry index k
+ * Entry 0 is the input state of every photon of the first queue (the interleaved
+ * clone ids of ncopies > 1 included, photon.py:242-247); entry k the state after
+ * k steps of the photons queued into step k, in queue order.  evidx is not
+ * stored: it is d_evidx[id].
+ *   order 0, step-major:   entry 0's records, entry 1's, ...; offsets[nentries + 1]
+ *   order 1, photon-major: photon 0's records by entry, photon 1's, ...;
+ *                          offsets[nphotons + 1] (a photon queued at step k was
+ *                          queued at every earlier step: its j-th record is entry j)
+ *
+ * chr_propagate_tracked is chr_propagate's host loop with one step per launch on
+ * every step (never the multi-step tail, never live records or device-driven
+ * slots; scatter_first on the first step only): where a step is one launch for
+ * chr_propagate (a slot count that is a multiple of 64) it is the split trace +
+ * shade launch here too, otherwise the chunk launches of chr_propagate_chunk.
+ * The RNG slot of a photon is its position in the step's chunk on every path,
+ * so photons, RNG states and records are those of the chunk loop driven from
+ * the host (photon.py:252-293), word for word.  The loop ends at max_steps or
+ * when the queue empties (photon.py:285-286); nentries = steps run + 1;
+ * max_steps == 0 records entry 0 and launches no step; nphotons == 0 gives a
+ * handle with one empty entry and launches nothing (the photon arrays' addresses
+ * may then be NULL).  The step-major buffer grows
+ * geometrically from capacity_hint records (0: nphotons x min(max_steps + 1, 2),
+ * what entries 0 and 1 take), never nphotons x (max_steps + 1) up front.
+ * CHR_ERR_INVALID before any launch for what chr_propagate refuses and a NULL out;
+ * CHR_ERR_NOMEM when a buffer cannot be allocated, CHR_ERR_INTERNAL when a queue
+ * word is not a photon of the call (counted on the device, never followed): then
+ * everything the call allocated is freed and *out is NULL.  stats as
+ * chr_propagate fills them; host_syncs <= steps run + 1.  Synchronous. */
+#define CHR_TRACK_WORDS 16
+typedef struct chr_tracks chr_tracks;   /* opaque, owns its device memory */
+int chr_propagate_tracked(const chr_geometry *g, const chr_photons *ph, uint32_t nphotons,
+                          uint32_t true_nphotons, uint32_t ncopies,
+                          uint32_t *d_rng_states, uint32_t rng_nslots,
+                          int32_t nthreads_per_block, int32_t max_blocks, int32_t max_steps,
+                          int32_t use_weights, int32_t scatter_first,
+                          uint64_t capacity_hint /* records; 0 = default */,
+                          chr_tracks **out, chr_propagate_stats *stats, void *stream);
+/* replaces: len(step_photon_ids) and the sum of its arrays' lengths (photon.py:252-293) */
+int chr_tracks_info(const chr_tracks *t, uint32_t *nentries, uint64_t *nrecords, uint32_t *nphotons);
+/* replaces: the lengths of step_photon_ids' arrays (photon.py:252-293) */
+int chr_tracks_entry_counts(const chr_tracks *t, uint64_t *h_counts /*[nentries]*/);
+/* the device buffers of one order (no reference counterpart, photon.py:252-293 keeps
+ * none): valid until chr_tracks_free; NULL records for an empty buffer */
+int chr_tracks_device(const chr_tracks *t, int32_t order /*0 step-major, 1 photon-major*/,
+                      const uint32_t **d_records, const uint64_t **d_offsets);
+/* replaces: the downloads of photon.py:252-293 (one .get() per array and step) with one
+ * copy: h_records[nrecords * CHR_TRACK_WORDS], h_offsets[nentries + 1 or nphotons + 1];
+ * either may be NULL */
+int chr_tracks_copy(const chr_tracks *t, int32_t order, uint32_t *h_records, uint64_t *h_offsets);
+/* NULL is accepted (as chr_bvh_result_free) */
+int chr_tracks_free(chr_tracks *t);
+/* replaces: the host arrays photon.py:252-293 gets from one .get() per array and step.
+ * Host only: record r of h_records (as chr_tracks_copy gives them, either order) goes to
+ * element r of the nine HOST arrays of h_out (nrecords photons) and its id to h_ids[r];
+ * evidx[r] = h_evidx[id] (h_evidx: nphotons words).  One pass, on the library's host
+ * threads.  CHR_ERR_INVALID for a NULL argument or an id >= nphotons (never followed). */
+int chr_tracks_unpack(const uint32_t *h_records, uint64_t nrecords, const uint32_t *h_evidx,
+                      uint32_t nphotons, const chr_photons *h_out, uint32_t *h_ids);
 
 /* ------------------------------------------------------------ selection */
 /* replaces: count_photon_hits + copy_photon_hits (propagate.cu:172-251),
