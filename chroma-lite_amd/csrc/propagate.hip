@@ -36,6 +36,8 @@
 #include "common.h"
 #include "device_geometry.h"
 #include "device_math.h"
+#include "grow_buffer.h"
+#include "prop_layout.h"
 #include "sampling.h"
 #include "slab_plane.h"
 #include "tracks.h"
@@ -4284,46 +4286,43 @@ int get_jump_tables(JumpTables &jt) {
     return CHR_OK;
 }
 
-// device scratch reused by the selection helpers (per thread, grown on demand)
-struct Scratch {
-    void *ptr = nullptr;
-    size_t bytes = 0;
-    int device = -1;
-};
-
+// The device buffers the drivers keep: one per pool, thread, device and context, grown on
+// demand (grow_buffer.h: a failed grow leaves the buffer empty, never a size without memory).
 // ctx: which of a thread's NCTX propagate buffer contexts (chr_propagate_batches
 // rotates them so batches can overlap: a tail, the next batches' first steps)
 constexpr int NCTX = 3;
-int scratch_get(size_t bytes, void **out, int ctx = 0) {
-    static thread_local Scratch s[NCTX][16];
+enum Pool {
+    POOL_SCRATCH,      // a propagate's allocation (prop_bufs), the selection helpers' scratch
+    POOL_WALK_STACK,   // HBM column for the deep walk-stack entries of the persistent trace grid (trace_kernel)
+    POOL_FLAT,         // FlatCtx::ctl
+    POOL_SLOT_CTL,     // per-slot control words of a device-driven propagate (device_slots)
+    POOL_RENDER,       // chr_render's rank scratch
+};
+template <Pool P>
+int pool_grow(size_t bytes, void **out, int ctx) {
+    static thread_local GrowBuffer s[NCTX][16];
     int dev = 0;
     CHR_HIP_CHECK(hipGetDevice(&dev));
-    Scratch &x = s[ctx % NCTX][dev & 15];
-    if (x.bytes < bytes) {
-        if (x.ptr) CHR_HIP_CHECK(hipFree(x.ptr));
-        x.ptr = nullptr;
-        CHR_HIP_CHECK(hipMalloc(&x.ptr, bytes));
-        x.bytes = bytes;
-    }
+    GrowBuffer &x = s[ctx % NCTX][dev & 15];
+    const int rc = grow_buffer(
+        x, bytes,
+        [](void **p, size_t n) -> int {
+            CHR_HIP_CHECK(hipMalloc(p, n));
+            return CHR_OK;
+        },
+        [](void *p) -> int {
+            CHR_HIP_CHECK(hipFree(p));
+            return CHR_OK;
+        });
     *out = x.ptr;
-    return CHR_OK;
+    return rc;
 }
-
-// HBM column for the deep walk-stack entries of the persistent trace grid
-// (per thread and device, grown on demand; see trace_kernel)
-int walk_stack_get(size_t bytes, uint2 **out, int ctx = 0) {
-    static thread_local Scratch s[NCTX][16];
-    int dev = 0;
-    CHR_HIP_CHECK(hipGetDevice(&dev));
-    Scratch &x = s[ctx % NCTX][dev & 15];
-    if (x.bytes < bytes) {
-        if (x.ptr) CHR_HIP_CHECK(hipFree(x.ptr));
-        x.ptr = nullptr;
-        CHR_HIP_CHECK(hipMalloc(&x.ptr, bytes));
-        x.bytes = bytes;
-    }
-    *out = (uint2 *)x.ptr;
-    return CHR_OK;
+template <Pool P, class T>
+int pool_get(size_t bytes, T **out, int ctx = 0) {
+    void *p = nullptr;
+    const int rc = pool_grow<P>(bytes, &p, ctx);
+    *out = (T *)p;
+    return rc;
 }
 
 }  // namespace
@@ -4376,14 +4375,9 @@ static size_t sort_temp_bytes16(uint32_t n, int bits = 24) {
 // Morton cells, 4.55 with Hilbert order (490.3 -> 500.3 M/s); photons identical.
 constexpr int BIN_KEY_BITS = 22;
 // u32 words: [0..15] counters | masks (2 per 64 slots) | offsets (1 per 64) |
-// block prefixes (1 per 256 words, +2)
-static uint64_t mask_scan_words(uint64_t n) {   // masks + offsets + block prefixes for n positions
-    const uint64_t nwords = (n + 63) / 64;
-    return 2 * nwords + nwords + scan_blocks((uint32_t)nwords) + 2;
-}
-extern "C" uint64_t chr_propagate_scratch_words(uint32_t nthreads) {
-    return 16 + mask_scan_words(nthreads) + 64;
-}
+// block prefixes (1 per 256 words, +2): prop_layout.h
+static_assert(SCAN_WORDS == LAYOUT_SCAN_WORDS && LIVE_QUADS == LAYOUT_LIVE_QUADS, "prop_layout.h: kernel constants");
+extern "C" uint64_t chr_propagate_scratch_words(uint32_t nthreads) { return chunk_scratch_words(nthreads); }
 
 // Kernel variants (CHR_PROPAGATE_VARIANT=<n>, read per launch so one process
 // can A/B them; every variant gives identical results -- tools/ab_variants.py
@@ -4525,21 +4519,28 @@ static StepVariant select_step_variant(const chr_geometry *g) {
 // scratch layout (u32 words): [0] overflows [1] queue base [2..11] u64 walk counters [12..15] pad; masks (u64, 8-aligned); offsets
 static bool pair_walk_enabled();
 static uint32_t walk_up_mode();
-static int launch_chunk(const chr_geometry *g, const chr_photons *ph, uint32_t *rng, uint32_t nslots, int32_t first,
-                        int32_t nthreads, const uint32_t *in_queue, uint32_t *out_queue, int32_t max_steps,
-                        int32_t use_weights, int32_t scatter_first, uint32_t *scratch, hipStream_t stream,
-                        hipEvent_t ev0 = nullptr, hipEvent_t ev1 = nullptr) {
-    const uint32_t nwords = (uint32_t)((nthreads + 63) / 64);
-    uint32_t *counters = scratch;               // [0] overflows, [1] base
-    unsigned long long *masks = (unsigned long long *)(scratch + 16);
+struct StepScratch {
+    uint32_t *counters;          // [0] overflows, [1] base
+    unsigned long long *masks;   // alive bits per queue position
+    uint32_t *offsets, *bsums;   // their scan: word offsets, block prefixes
+    uint32_t nwords;
+};
+static StepScratch step_scratch(uint32_t *scratch, uint32_t n) {
+    const uint32_t nwords = (n + 63) / 64;
     uint32_t *offsets = scratch + 16 + 2 * (size_t)nwords;
-    uint32_t *bsums = offsets + nwords;
+    return StepScratch{scratch, (unsigned long long *)(scratch + 16), offsets, offsets + nwords, nwords};
+}
+
+// the arguments of a launch over nthreads queue positions from `first`, one step kernel for all of them
+static PropagateArgs propagate_args(const chr_photons *ph, uint32_t *rng, uint32_t nslots, const uint32_t *in_queue,
+                                    int32_t first, int32_t nthreads, int32_t max_steps, int32_t use_weights,
+                                    int32_t scatter_first, const StepScratch &s) {
     PropagateArgs a;
     a.pos = ph->d_pos; a.dir = ph->d_dir; a.pol = ph->d_pol; a.wl = ph->d_wavelengths; a.t = ph->d_t;
     a.weights = ph->d_weights; a.flags = ph->d_flags; a.last_hit = ph->d_last_hit_triangles; a.evidx = ph->d_evidx;
     a.rng = rng; a.nslots = nslots; a.input_queue = in_queue; a.first = first; a.nthreads = nthreads;
     a.max_steps = max_steps; a.use_weights = use_weights; a.scatter_first = scatter_first;
-    a.alive_masks = masks; a.counters = counters;
+    a.alive_masks = s.masks; a.counters = s.counters;
     a.order = nullptr;
     a.hits = nullptr;
     a.diag = nullptr;
@@ -4551,15 +4552,34 @@ static int launch_chunk(const chr_geometry *g, const chr_photons *ph, uint32_t *
     a.prio = 0;
     a.pair = pair_walk_enabled() ? 1u : 0u;
     a.walk_up = walk_up_mode();
+    return a;
+}
+
+// the alive masks' scan and the scatter of the survivors into out_queue (device-driven, a.dev_n:
+// a bounded grid-stride scatter; slots of mode `skip` leave no queue)
+static void scan_scatter(const StepScratch &s, const PropagateArgs &a, uint32_t *out_queue, const RayEnrol &fe,
+                         uint32_t skip, const HeadNext *hn, const LiveCarry &lc, hipStream_t stream) {
+    launch_mask_scan(s.masks, s.nwords, s.offsets, s.bsums, out_queue, s.counters + 1, nullptr, stream, a.dev_n, a.mode,
+                     skip, hn);
+    const unsigned grid = grid_for(a.nthreads);
+    hipLaunchKernelGGL(scatter_queue_kernel, dim3(a.dev_n ? std::min(4096u, grid) : grid), dim3(BLOCK), 0, stream,
+                       s.masks, s.offsets, s.bsums, s.counters + 1, a.input_queue, a.first, a.nthreads, out_queue, fe,
+                       a.dev_n, a.mode, skip, lc);
+}
+
+static int launch_chunk(const chr_geometry *g, const chr_photons *ph, uint32_t *rng, uint32_t nslots, int32_t first,
+                        int32_t nthreads, const uint32_t *in_queue, uint32_t *out_queue, int32_t max_steps,
+                        int32_t use_weights, int32_t scatter_first, uint32_t *scratch, hipStream_t stream,
+                        hipEvent_t ev0 = nullptr, hipEvent_t ev1 = nullptr) {
+    const StepScratch s = step_scratch(scratch, (uint32_t)nthreads);
+    const PropagateArgs a = propagate_args(ph, rng, nslots, in_queue, first, nthreads, max_steps, use_weights,
+                                           scatter_first, s);
     if (ev0) CHR_HIP_CHECK(hipEventRecord(ev0, stream));
     hipLaunchKernelGGL(select_variant(g), dim3(grid_for(nthreads)), dim3(BLOCK), 0, stream,
                        (const DevGeom *)g->d_dev, a);
     if (ev1) CHR_HIP_CHECK(hipEventRecord(ev1, stream));
-    launch_mask_scan(masks, nwords, offsets, bsums, out_queue, counters + 1, nullptr, stream);
-    hipLaunchKernelGGL(scatter_queue_kernel, dim3(grid_for(nthreads)), dim3(BLOCK), 0, stream, masks, offsets, bsums,
-                       counters + 1, in_queue, first, nthreads, out_queue,
-                       RayEnrol{nullptr, nullptr, nullptr, nullptr}, (const uint32_t *)nullptr,
-                       (const uint32_t *)nullptr, STEP_IDLE, LiveCarry{nullptr, nullptr, nullptr, a});
+    scan_scatter(s, a, out_queue, RayEnrol{nullptr, nullptr, nullptr, nullptr}, STEP_IDLE, nullptr,
+                 LiveCarry{nullptr, nullptr, nullptr, a}, stream);
     CHR_HIP_CHECK(hipGetLastError());
     return CHR_OK;
 }
@@ -4590,22 +4610,9 @@ struct FlatCtx {
     // queue in live[k & 1]
     uint4 *live[2] = {nullptr, nullptr};
 };
-static int flat_get(uint32_t n, FlatCtx &fc, int ctx = 0) {
-    static thread_local Scratch s[NCTX][16];
-    int dev = 0;
-    CHR_HIP_CHECK(hipGetDevice(&dev));
-    Scratch &x = s[ctx % NCTX][dev & 15];
-    (void)n;
-    const size_t bytes = 256;
-    if (x.bytes < bytes) {
-        if (x.ptr) CHR_HIP_CHECK(hipFree(x.ptr));
-        x.ptr = nullptr;
-        CHR_HIP_CHECK(hipMalloc(&x.ptr, bytes));
-        x.bytes = bytes;
-    }
-    fc.ctl = (uint32_t *)x.ptr;
+static int flat_get(FlatCtx &fc, int ctx = 0) {
     fc.enrol_next = false;
-    return CHR_OK;
+    return pool_get<POOL_FLAT>(256, &fc.ctl, ctx);
 }
 
 static bool trace_steps();
@@ -4676,10 +4683,9 @@ struct SlotCtl {
     int slot = 0;                     // the slot's index in its propagate
     bool live = false;                // the propagate's one-step slots carry live records (device_slots)
     uint32_t *host_ring = nullptr;    // pinned (mode, length) words the head kernel writes (nullptr: none)
-    // the next slot's head folded into this slot's block-sum scan (fold_head: every slot
-    // after the first then launches no head kernel of its own); next_head.ray_counter is
+    // the next slot's head, folded into this slot's block-sum scan when set (every slot
+    // after the first launches no head kernel of its own); next_head.ray_counter is
     // filled by launch_step
-    bool fold_head = false;
     HeadNext next_head{nullptr, nullptr, nullptr, nullptr, nullptr, 0u, 0u, 0, 0};
     hipEvent_t prefix_done = nullptr, ev_rest0 = nullptr;
 };
@@ -4705,39 +4711,76 @@ static unsigned tail_grid(const StepVariant &sv, uint32_t threads, bool work_que
     return std::max(1u, std::min(full, resident));
 }
 
-static int launch_step(const chr_geometry *g, const chr_photons *ph, uint32_t *rng, uint32_t nslots, uint32_t cap,
-                       uint32_t n, const uint32_t *in_queue, uint32_t *out_queue, int32_t max_steps,
-                       int32_t use_weights, int32_t scatter_first, uint32_t *scratch, hipStream_t stream,
-                       hipEvent_t ev0, hipEvent_t ev1, int2 *hits, uint32_t *sort_space, bool first_step,
-                       hipEvent_t evt0, hipEvent_t evt1, bool *split_out, const FlatCtx *fc,
+// What every launch of one propagate shares: built once (step_ctx).
+struct StepCtx {
+    const chr_geometry *g;
+    const chr_photons *ph;
+    uint32_t *rng;
+    uint32_t nslots;
+    uint32_t cap;             // slots of one chunk
+    int32_t use_weights;
+    char *base;               // the propagate's allocation and where its regions lie (prop_bufs)
+    PropLayout lay;
+    uint32_t *scratch;
+    int2 *hits;               // nullptr: not fused (no split path)
+    const FlatCtx *fc;        // the propagate's PropBufs::fc
+    hipStream_t stream;
+};
+
+// the timing events of one launch_step (nullptr: not recorded): ev0 / ev1 around the step's
+// kernels, evt0 / evt1 around its trace launch
+struct StepEvents {
+    hipEvent_t ev0, ev1, evt0, evt1;
+};
+
+// blocks of a trace launch over n rays: the persistent grid, or fewer when n is small
+static uint32_t trace_blocks(const StepVariant &sv, uint64_t n) {
+    const uint64_t tb = (uint64_t)sv.trace_block;
+    const uint64_t resident = (uint64_t)device_cus() * 4 * sv.trace_waves * 64 / tb;
+    return (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(resident, (n + tb - 1) / tb));
+}
+
+// The tail kernel over the step's queue on stream s, every remaining step (`steps`), its alive
+// bits OR-ed into cleared mask words; `a` by value: the one-step arguments.
+static int launch_tail(const StepCtx &c, const StepVariant &sv, PropagateArgs a, unsigned long long *masks,
+                       uint32_t nwords, uint32_t threads, int32_t steps, uint32_t *next, const SlotCtl *sc,
+                       hipStream_t s) {
+    // few workgroups (grid-stride): a tail holds < nthreads_per_block * 128 photons
+    // unless use_weights, and on a tail stream this launch waits for free CU slots beside the
+    // next batch's persistent walk grid -- a 1024-workgroup clear measured
+    // 125 us per slot (r03 rocprof), every slot's on the tail's stream
+    if (sc) hipLaunchKernelGGL(clear_masks_kernel, dim3(std::min<uint32_t>(kClearBlocks, grid_for(nwords))), dim3(BLOCK), 0,
+                               s, masks, a.dev_n, a.mode);
+    else CHR_HIP_CHECK(hipMemsetAsync(masks, 0, (size_t)nwords * 8, s));
+    a.alive_masks = masks;
+    a.max_steps = steps;
+    a.want = STEP_TAIL;
+    a.work = (next && tail_work_queue(sv, sc, c.use_weights, c.cap)) ? next : nullptr;
+    hipLaunchKernelGGL(sv.tail, dim3(tail_grid(sv, threads, a.work != nullptr)), dim3(BLOCK),
+                       phys_lds_bytes(c.g->dev, TAIL_PHYS_WORDS), s, (const DevGeom *)c.g->d_dev, a, c.cap);
+    return CHR_OK;
+}
+
+// One step over the n queued photons of in_queue (slot = queue position mod cap), the
+// survivors into out_queue.  sc: a device-driven slot (SlotCtl).
+static int launch_step(const StepCtx &c, uint32_t n, const uint32_t *in_queue, uint32_t *out_queue, int32_t max_steps,
+                       int32_t scatter_first, bool first_step, const StepEvents &e, bool *split_out,
                        const SlotCtl *sc = nullptr) {
-    const uint32_t nwords = (n + 63) / 64;
-    uint32_t *counters = scratch;
-    unsigned long long *masks = (unsigned long long *)(scratch + 16);
-    uint32_t *offsets = scratch + 16 + 2 * (size_t)nwords;
-    uint32_t *bsums = offsets + nwords;
-    const uint32_t *dev_n = sc ? in_queue - 1 : nullptr;   // the input queue's count header
-    const uint32_t *mode = sc ? sc->mode : nullptr;
-    PropagateArgs a;
-    a.pos = ph->d_pos; a.dir = ph->d_dir; a.pol = ph->d_pol; a.wl = ph->d_wavelengths; a.t = ph->d_t;
-    a.weights = ph->d_weights; a.flags = ph->d_flags; a.last_hit = ph->d_last_hit_triangles; a.evidx = ph->d_evidx;
-    a.rng = rng; a.nslots = nslots; a.input_queue = in_queue; a.first = 0; a.nthreads = (int32_t)n;
-    a.max_steps = max_steps; a.use_weights = use_weights; a.scatter_first = scatter_first;
-    a.alive_masks = masks; a.counters = counters;
-    a.order = nullptr;
-    a.hits = nullptr;
+    const chr_geometry *g = c.g;
+    const chr_photons *ph = c.ph;
+    const FlatCtx *fc = c.fc;
+    int2 *hits = c.hits;
+    const int32_t use_weights = c.use_weights;
+    hipStream_t stream = c.stream;
+    const StepScratch s = step_scratch(c.scratch, n);
+    PropagateArgs a = propagate_args(ph, c.rng, c.nslots, in_queue, 0, (int32_t)n, max_steps, use_weights,
+                                     scatter_first, s);
     a.diag = fc ? fc->ctl + 4 : nullptr;
-    a.dev_n = dev_n;
-    a.mode = mode;
-    a.want = STEP_ONE;
-    a.work = nullptr;
-    a.live = nullptr;
-    a.prio = 0;
-    a.pair = pair_walk_enabled() ? 1u : 0u;
-    a.walk_up = walk_up_mode();
+    a.dev_n = sc ? in_queue - 1 : nullptr;   // the input queue's count header
+    a.mode = sc ? sc->mode : nullptr;
     RayEnrol fe{nullptr, nullptr, nullptr, nullptr};
     LiveCarry lc{nullptr, nullptr, nullptr, a};
-    const uint32_t threads = std::min(cap, (n + 63u) & ~63u);
+    const uint32_t threads = std::min(c.cap, (n + 63u) & ~63u);
     const StepVariant sv = select_step_variant(g);
     // host-driven: the split when this launch is one step; device-driven: the
     // one-step kernels and the tail kernel are both queued and the head picks
@@ -4745,24 +4788,25 @@ static int launch_step(const chr_geometry *g, const chr_photons *ph, uint32_t *r
     const bool tail = sv.tail && (sc ? sc->remaining > 1 : (!split && max_steps > 1));
     // the first step's length and mode are known on the host (binning, flat-walk enrolment)
     const bool first_one_step = first_step && (!sc || !((n < sc->tail_below || use_weights) && sc->remaining > 1));
-    uint32_t *next = split ? (uint32_t *)(hits + (sc ? sc->n_layout : n)) : nullptr;
+    const StepLayout sl = step_layout(c.lay, sc ? sc->n_layout : n, n);
+    uint32_t *next = split ? (uint32_t *)(c.base + sl.next) : nullptr;
     const int phase = sc ? sc->phase : PHASE_ALL;
     const bool pre = phase != PHASE_REST, rest = phase == PHASE_ALL || phase == PHASE_REST;
     if (phase != PHASE_ALL && (!split || !sc->prefix_done))
         return chr::fail(CHR_ERR_INVALID, "launch_step: a split slot needs the split path and its prefix event");
-    if (ev0 && pre) CHR_HIP_CHECK(hipEventRecord(ev0, stream));
+    if (e.ev0 && pre) CHR_HIP_CHECK(hipEventRecord(e.ev0, stream));
     if (!pre) {
         CHR_HIP_CHECK(hipStreamWaitEvent(stream, sc->prefix_done, 0));
         if (sc->ev_rest0) CHR_HIP_CHECK(hipEventRecord(sc->ev_rest0, stream));
     }
-    // the next slot's head, folded into this slot's scan (SlotCtl::fold_head)
+    // the next slot's head, folded into this slot's scan (SlotCtl::next_head)
     HeadNext hn{nullptr, nullptr, nullptr, nullptr, nullptr, 0u, 0u, 0, 0};
-    if (sc && sc->fold_head && sc->next_head.mode && next) {
+    if (sc && sc->next_head.mode && next) {
         hn = sc->next_head;
         hn.ray_counter = next;
     }
     const HeadNext *hnp = hn.mode ? &hn : nullptr;
-    if (sc && pre && !(sc->fold_head && !first_step)) {
+    if (sc && pre && first_step) {   // later slots' heads ran in the scan before them
         if (!next) return chr::fail(CHR_ERR_INVALID, "launch_step: device-driven steps need the split path");
         hipLaunchKernelGGL(step_head_kernel, dim3(1), dim3(64), 0, stream, in_queue - 1, out_queue, sc->mode, sc->nk,
                            sc->done, next, sc->tail_below, sc->remaining, use_weights, sc->n_layout, sc->host_ring);
@@ -4776,7 +4820,7 @@ static int launch_step(const chr_geometry *g, const chr_photons *ph, uint32_t *r
         const bool binned = (sv.binned == 1 || (sv.binned == 2 && first_one_step && n >= kBinFirstMin)) &&
                             (!sc || first_one_step);
         const bool bin_now = binned && pre;
-        uint32_t *keys = next + 16, *order = keys + n;
+        uint32_t *keys = (uint32_t *)(c.base + sl.keys), *order = (uint32_t *)(c.base + sl.order);
         // ray records: the first step's from its classification, later steps' from
         // the previous step's scatter (enrol_next)
         const bool use_rays = fc->rays && (first_one_step || fc->enrol_next);
@@ -4786,24 +4830,24 @@ static int launch_step(const chr_geometry *g, const chr_photons *ph, uint32_t *r
                                bin_now ? order : nullptr, use_rays ? fc->rays : nullptr);
         TraceArgs ta;
         ta.pos = ph->d_pos; ta.dir = ph->d_dir; ta.flags = ph->d_flags; ta.last_hit = ph->d_last_hit_triangles;
-        ta.queue = in_queue; ta.n = n; ta.hits = hits; ta.next = next; ta.counters = counters; ta.order = nullptr;
+        ta.queue = in_queue; ta.n = n; ta.hits = hits; ta.next = next; ta.counters = s.counters; ta.order = nullptr;
         ta.rays = use_rays ? fc->rays : nullptr;
         ta.walk_hist = nullptr;
         ta.diag = fc->ctl + 3;
-        ta.dev_n = dev_n;
-        ta.mode = mode;
+        ta.dev_n = a.dev_n;
+        ta.mode = a.mode;
         if (fc->enrol_next) fe = RayEnrol{ph->d_pos, ph->d_dir, fc->rays, ph->d_last_hit_triangles};
         if (trace_steps() && pre) {   // debugging: per-walk cost histogram (counting variants), printed per step
-            ta.walk_hist = next + 16 + 2 * (size_t)(sc ? sc->n_layout : n);
+            ta.walk_hist = (uint32_t *)(c.base + sl.walk_hist);
             CHR_HIP_CHECK(hipMemsetAsync(ta.walk_hist, 0, 34 * 4, stream));
         }
         if (binned) {
-            uint32_t *keys_out = sort_space, *vals_out = keys_out + n;
+            uint32_t *keys_out = (uint32_t *)(c.base + sl.keys_out), *vals_out = (uint32_t *)(c.base + sl.vals_out);
             if (bin_now) {
                 if (!first_one_step)   // the first step's keys came with its classification
                     hipLaunchKernelGGL(bin_key_kernel, dim3(grid_for(n)), dim3(BLOCK), 0, stream, ph->d_dir, in_queue,
                                        n, keys, order);
-                void *temp = (void *)(((uintptr_t)(vals_out + n) + 255) & ~(uintptr_t)255);
+                void *temp = c.base + sl.temp;
                 size_t temp_bytes = sort_temp_bytes16(n, BIN_KEY_BITS);
                 CHR_HIP_CHECK(rocprim::radix_sort_pairs(temp, temp_bytes, keys, keys_out, order, vals_out, n, 0,
                                                         BIN_KEY_BITS, stream));
@@ -4815,17 +4859,16 @@ static int launch_step(const chr_geometry *g, const chr_photons *ph, uint32_t *r
             if (use_rays) ta.rays = fc->rays_walk;
         }
         if (pre) {
-            const int cus = device_cus();
-            if (cus <= 0) return chr::fail(CHR_ERR_HIP, "launch_step: no compute units");
+            if (device_cus() <= 0) return chr::fail(CHR_ERR_HIP, "launch_step: no compute units");
             const int tb = sv.trace_block;
-            const uint64_t resident = (uint64_t)cus * 4 * sv.trace_waves * 64 / tb;   // persistent grid
-            const uint32_t blocks = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(resident, ((uint64_t)n + tb - 1) / tb));
-            if (int rc = walk_stack_get((size_t)WIDE_STACK * blocks * tb * sizeof(uint2), &ta.spill, sc ? sc->ctx : 0))
+            const uint32_t blocks = trace_blocks(sv, n);
+            if (int rc = pool_get<POOL_WALK_STACK>((size_t)WIDE_STACK * blocks * tb * sizeof(uint2), &ta.spill,
+                                                   sc ? sc->ctx : 0))
                 return rc;
-            if (evt0) CHR_HIP_CHECK(hipEventRecord(evt0, stream));
+            if (e.evt0) CHR_HIP_CHECK(hipEventRecord(e.evt0, stream));
             hipLaunchKernelGGL(ta.rays ? sv.trace : sv.trace_gather, dim3(blocks), dim3(tb), 0, stream,
                                (const DevGeom *)g->d_dev, ta);
-            if (evt1) CHR_HIP_CHECK(hipEventRecord(evt1, stream));
+            if (e.evt1) CHR_HIP_CHECK(hipEventRecord(e.evt1, stream));
         }
         if (!rest) {
             CHR_HIP_CHECK(hipEventRecord(sc->prefix_done, stream));
@@ -4846,7 +4889,7 @@ static int launch_step(const chr_geometry *g, const chr_photons *ph, uint32_t *r
         }
         if (sc && sc->rng_ready) CHR_HIP_CHECK(hipStreamWaitEvent(stream, sc->rng_ready, 0));
         hipLaunchKernelGGL(shade, dim3(grid_for(threads)), dim3(BLOCK), phys_lds_bytes(g->dev, SHADE_PHYS_WORDS), stream,
-                           (const DevGeom *)g->d_dev, a, cap);
+                           (const DevGeom *)g->d_dev, a, c.cap);
     }
     if (split_out) *split_out = split;
     if (tail && sc && sc->tail_stream) {   // the tail on its own stream (chr_propagate_batches)
@@ -4860,54 +4903,27 @@ static int launch_step(const chr_geometry *g, const chr_photons *ph, uint32_t *r
         // states the tail reads were last written by kernels ordered before ev0 on
         // `stream`, or by the previous batch's tail, earlier on this same tail stream.
         // tests/test_gpu_batches.py checks CHR_SLOT_TIMING=0 / 1 give identical photons.
-        hipEvent_t dep = ev1 ? ev1 : evt0;
+        hipEvent_t dep = e.ev1 ? e.ev1 : e.evt0;
         if (!dep) return chr::fail(CHR_ERR_INVALID, "launch_step: a tail stream needs a slot event");
         hipStream_t ts = sc->tail_stream;
-        if (ev1) CHR_HIP_CHECK(hipEventRecord(ev1, stream));
+        if (e.ev1) CHR_HIP_CHECK(hipEventRecord(e.ev1, stream));
         CHR_HIP_CHECK(hipStreamWaitEvent(ts, dep, 0));
         if (sc->evt_tail0) CHR_HIP_CHECK(hipEventRecord(sc->evt_tail0, ts));
-        // few workgroups (grid-stride): a tail holds < nthreads_per_block * 128 photons
-        // unless use_weights, and this launch waits for free CU slots beside the
-        // next batch's persistent walk grid -- a 1024-workgroup clear measured
-        // 125 us per slot (r03 rocprof), every slot's on the tail's stream
-        hipLaunchKernelGGL(clear_masks_kernel, dim3(std::min<uint32_t>(kClearBlocks, grid_for(nwords))), dim3(BLOCK), 0, ts,
-                           sc->tail_masks, dev_n, mode);
         PropagateArgs at = a;
         at.prio = 1u;
-        at.alive_masks = sc->tail_masks;
-        at.max_steps = sc->remaining;
-        at.want = STEP_TAIL;
-        at.work = tail_work_queue(sv, sc, use_weights, cap) ? next : nullptr;
-        hipLaunchKernelGGL(sv.tail, dim3(tail_grid(sv, threads, at.work != nullptr)), dim3(BLOCK),
-                           phys_lds_bytes(g->dev, TAIL_PHYS_WORDS), ts,
-                           (const DevGeom *)g->d_dev, at, cap);
+        CHR_TRY(launch_tail(c, sv, at, sc->tail_masks, s.nwords, threads, sc->remaining, next, sc, ts));
         if (sc->evt_tail1) CHR_HIP_CHECK(hipEventRecord(sc->evt_tail1, ts));
-        launch_mask_scan(masks, nwords, offsets, bsums, out_queue, counters + 1, nullptr, stream, dev_n, mode, STEP_TAIL,
-                         hnp);
-        hipLaunchKernelGGL(scatter_queue_kernel, dim3(std::min<uint32_t>(4096u, grid_for(n))), dim3(BLOCK), 0, stream,
-                           masks, offsets, bsums, counters + 1, in_queue, 0, (int32_t)n, out_queue, fe, dev_n, mode,
-                           STEP_TAIL, lc);
+        scan_scatter(s, a, out_queue, fe, STEP_TAIL, hnp, lc, stream);
         CHR_HIP_CHECK(hipGetLastError());
         return CHR_OK;
     }
-    if (tail) {   // group / wave-adaptive walk, alive bits OR-ed into zeroed words
-        if (sc) hipLaunchKernelGGL(clear_masks_kernel, dim3(std::min<uint32_t>(kClearBlocks, grid_for(nwords))), dim3(BLOCK), 0,
-                                   stream, masks, dev_n, mode);
-        else CHR_HIP_CHECK(hipMemsetAsync(masks, 0, (size_t)nwords * 8, stream));
-        a.max_steps = sc ? sc->remaining : max_steps;
-        a.want = STEP_TAIL;
-        a.work = (sc && next && tail_work_queue(sv, sc, use_weights, cap)) ? next : nullptr;
-        hipLaunchKernelGGL(sv.tail, dim3(tail_grid(sv, threads, a.work != nullptr)), dim3(BLOCK),
-                           phys_lds_bytes(g->dev, TAIL_PHYS_WORDS), stream,
-                           (const DevGeom *)g->d_dev, a, cap);
+    if (tail) {   // group / wave-adaptive walk
+        CHR_TRY(launch_tail(c, sv, a, s.masks, s.nwords, threads, sc ? sc->remaining : max_steps, next, sc, stream));
     } else if (!split) {
-        hipLaunchKernelGGL(sv.fn, dim3(grid_for(threads)), dim3(BLOCK), 0, stream, (const DevGeom *)g->d_dev, a, cap);
+        hipLaunchKernelGGL(sv.fn, dim3(grid_for(threads)), dim3(BLOCK), 0, stream, (const DevGeom *)g->d_dev, a, c.cap);
     }
-    if (ev1) CHR_HIP_CHECK(hipEventRecord(ev1, stream));
-    launch_mask_scan(masks, nwords, offsets, bsums, out_queue, counters + 1, nullptr, stream, dev_n, mode, STEP_IDLE, hnp);
-    hipLaunchKernelGGL(scatter_queue_kernel, dim3(sc ? std::min<uint32_t>(4096u, grid_for(n)) : grid_for(n)), dim3(BLOCK),
-                       0, stream, masks, offsets, bsums, counters + 1, in_queue, 0, (int32_t)n, out_queue, fe, dev_n,
-                       mode, STEP_IDLE, lc);
+    if (e.ev1) CHR_HIP_CHECK(hipEventRecord(e.ev1, stream));
+    scan_scatter(s, a, out_queue, fe, STEP_IDLE, hnp, lc, stream);
     CHR_HIP_CHECK(hipGetLastError());
     return CHR_OK;
 }
@@ -4937,19 +4953,23 @@ static int pinned_words(uint32_t **out, int ctx = 0) {
     return CHR_OK;
 }
 
-// timing events, reused across calls (per thread)
-static int timing_events(size_t n, std::vector<hipEvent_t> **out, int ctx = 0) {
-    static thread_local std::vector<hipEvent_t> ev[2][16];
-    int dev = 0;
-    CHR_HIP_CHECK(hipGetDevice(&dev));
-    std::vector<hipEvent_t> &v = ev[ctx & 1][dev & 15];
+// grow an event list to n events
+static int grow_events(std::vector<hipEvent_t> &v, size_t n) {
     while (v.size() < n) {
         hipEvent_t e;
         CHR_HIP_CHECK(hipEventCreate(&e));
         v.push_back(e);
     }
-    *out = &v;
     return CHR_OK;
+}
+
+// timing events, reused across calls (per thread)
+static int timing_events(size_t n, std::vector<hipEvent_t> **out, int ctx = 0) {
+    static thread_local std::vector<hipEvent_t> ev[2][16];
+    int dev = 0;
+    CHR_HIP_CHECK(hipGetDevice(&dev));
+    *out = &ev[ctx & 1][dev & 15];
+    return grow_events(**out, n);
 }
 
 static bool trace_steps() {   // CHR_TRACE_STEPS=1: one stderr line per host step (debugging)
@@ -4969,20 +4989,18 @@ static bool host_steps_forced() {     // CHR_HOST_STEPS=1: read the survivor cou
 
 // per-slot control words of a device-driven propagate: [2k] mode, [2k + 1]
 // queue length of slot k, then the done flag (per thread and device, grown on demand)
-static int slot_ctl_get(size_t words, uint32_t **out, int ctx = 0) {
-    static thread_local Scratch s[NCTX][16];
-    int dev = 0;
-    CHR_HIP_CHECK(hipGetDevice(&dev));
-    Scratch &x = s[ctx % NCTX][dev & 15];
-    if (x.bytes < words * 4) {
-        if (x.ptr) CHR_HIP_CHECK(hipFree(x.ptr));
-        x.ptr = nullptr;
-        CHR_HIP_CHECK(hipMalloc(&x.ptr, words * 4));
-        x.bytes = words * 4;
-    }
-    *out = (uint32_t *)x.ptr;
-    return CHR_OK;
+static int slot_ctl_get(int32_t max_steps, uint32_t **out, int ctx = 0) {
+    return pool_get<POOL_SLOT_CTL>((2 * (size_t)max_steps + 8) * 4, out, ctx);
 }
+
+// The launch-shape rules (photon.py, tools.py): slots of one chunk, and whether one launch
+// covers a step -- when a wave's 64 slots map to whole mask words
+static bool fused_ok(int32_t ntpb, int32_t max_blocks) {
+    const uint64_t cap = (uint64_t)ntpb * max_blocks;
+    return (cap % 64 == 0) && cap <= 0x7FFFFFFFull && step_launch_enabled();
+}
+// the nsteps policy's threshold (photon.py:261-264): queues below it run every remaining step in one launch
+static uint32_t tail_below(int32_t ntpb) { return (uint32_t)ntpb * 16 * 8; }
 
 // per-slot events of a device-driven propagate: [0] slot start, [1] its
 // one-step kernels done (with the tail when that runs on the same stream),
@@ -4997,10 +5015,11 @@ constexpr int SLOT_EVENTS = 8;
 struct PropBufs {
     uint64_t cap = 0;        // slots of one chunk, nthreads_per_block * max_blocks
     bool fused = false;      // one launch per step
+    char *base = nullptr;    // the allocation; lay: where its regions lie (prop_layout.h)
+    PropLayout lay;
     uint32_t *q[2] = {nullptr, nullptr};
     uint32_t *scratch = nullptr;
     int2 *hits = nullptr;
-    uint32_t *sort_space = nullptr;
     unsigned long long *tail_masks = nullptr;
     uint32_t *pinned = nullptr;
     FlatCtx fc{};
@@ -5009,40 +5028,30 @@ struct PropBufs {
 
 static int prop_bufs(uint32_t nphotons, int32_t ntpb, int32_t max_blocks, int ctx, bool tail_masks, PropBufs &b) {
     b.cap = (uint64_t)ntpb * max_blocks;   // slots of one chunk (chunk_iterator)
-    const uint32_t chunk_cap = (uint32_t)std::min<uint64_t>(b.cap, nphotons);
-    // one launch per step when a wave's 64 slots map to whole mask words
-    b.fused = (b.cap % 64 == 0) && b.cap <= 0x7FFFFFFFull && step_launch_enabled();
-    uint64_t swords = chr_propagate_scratch_words(chunk_cap);
-    if (b.fused) swords = std::max<uint64_t>(swords, 16 + mask_scan_words(nphotons) + 16);
-    const size_t qbytes = ((size_t)nphotons + 1) * 4;
-    // split path: hits, ray counter, binning keys/order/histogram
-    const size_t hbytes = b.fused ? (size_t)nphotons * 24 + 128 + 256 + 512 + sort_temp_bytes16(nphotons) : 0;
-    // split path: ray records, queue order + walk order (FlatCtx::rays / rays_walk)
-    const size_t rbytes = b.fused ? (size_t)nphotons * 64 + 512 : 0;
-    // split path: live records, two buffers of 64 B per photon (FlatCtx::live)
-    const size_t lbytes = b.fused ? (size_t)nphotons * 128 + 512 : 0;
-    const size_t base_bytes = 2 * qbytes + swords * 4 + 64 + hbytes + rbytes + lbytes;
-    const size_t mbytes = tail_masks ? ((size_t)nphotons + 63) / 64 * 8 + 512 : 0;
-    void *buf = nullptr;
-    int rc = scratch_get(base_bytes + mbytes, &buf, ctx);
-    if (rc) return rc;
-    b.q[0] = (uint32_t *)buf;
-    b.q[1] = b.q[0] + (nphotons + 1);
-    b.scratch = (uint32_t *)(((uintptr_t)(b.q[1] + nphotons + 1) + 15) & ~(uintptr_t)15);
-    b.hits = b.fused ? (int2 *)(((uintptr_t)(b.scratch + swords) + 15) & ~(uintptr_t)15) : nullptr;
-    // radix-sort space after [hits][next+pad][keys][order][hist][walk hist]
-    b.sort_space = b.fused ? (uint32_t *)(((uintptr_t)((uint32_t *)(b.hits + nphotons) + 16 + 2 * (size_t)nphotons +
-                                                       64) + 255) & ~(uintptr_t)255) : nullptr;
-    b.tail_masks = tail_masks ? (unsigned long long *)(((uintptr_t)buf + base_bytes + 255) & ~(uintptr_t)255) : nullptr;
-    if ((rc = pinned_words(&b.pinned, ctx))) return rc;
-    if (b.fused && (rc = flat_get(nphotons, b.fc, ctx))) return rc;
+    b.fused = fused_ok(ntpb, max_blocks);
+    const PropLayout &l = b.lay = prop_layout(nphotons, b.cap, b.fused, tail_masks,
+                                              b.fused ? sort_temp_bytes16(nphotons) : 0);
+    CHR_TRY(pool_get<POOL_SCRATCH>(l.total, &b.base, ctx));
+    if ((uintptr_t)b.base & 255) return chr::fail(CHR_ERR_INTERNAL, "prop_bufs: device allocation not 256-aligned");
+    b.q[0] = (uint32_t *)(b.base + l.q[0]);
+    b.q[1] = (uint32_t *)(b.base + l.q[1]);
+    b.scratch = (uint32_t *)(b.base + l.scratch);
+    b.hits = b.fused ? (int2 *)(b.base + l.hits) : nullptr;
+    b.tail_masks = tail_masks ? (unsigned long long *)(b.base + l.tail_masks) : nullptr;
+    CHR_TRY(pinned_words(&b.pinned, ctx));
     if (b.fused) {
-        b.fc.rays = (uint4 *)(((uintptr_t)buf + 2 * qbytes + swords * 4 + 64 + hbytes + 255) & ~(uintptr_t)255);
-        b.fc.rays_walk = b.fc.rays + 2 * (size_t)nphotons;
-        b.fc.live[0] = (uint4 *)(((uintptr_t)(b.fc.rays_walk + 2 * (size_t)nphotons) + 255) & ~(uintptr_t)255);
-        b.fc.live[1] = b.fc.live[0] + LIVE_QUADS * (size_t)nphotons;
+        CHR_TRY(flat_get(b.fc, ctx));
+        b.fc.rays = (uint4 *)(b.base + l.rays);
+        b.fc.rays_walk = (uint4 *)(b.base + l.rays_walk);
+        b.fc.live[0] = (uint4 *)(b.base + l.live[0]);
+        b.fc.live[1] = (uint4 *)(b.base + l.live[1]);
     }
     return CHR_OK;
+}
+
+static StepCtx step_ctx(const chr_geometry *g, const chr_photons *ph, uint32_t *rng, uint32_t nslots,
+                        int32_t use_weights, const PropBufs &b, hipStream_t stream) {
+    return StepCtx{g, ph, rng, nslots, (uint32_t)b.cap, use_weights, b.base, b.lay, b.scratch, b.hits, &b.fc, stream};
 }
 
 // queues (photon.py:242-250: clones interleaved, q[1] header = 1), step counters, flat-walk control words
@@ -5053,16 +5062,6 @@ static int prop_start(const PropBufs &b, uint32_t nphotons, uint32_t true_nphoto
     hipLaunchKernelGGL(init_queue_kernel, dim3(grid_for(nphotons)), dim3(BLOCK), 0, stream, b.q[0], b.q[1], nphotons,
                        true_nphotons, ncopies, z);
     CHR_HIP_CHECK(hipGetLastError());
-    return CHR_OK;
-}
-
-// grow a slot event list to n events
-static int grow_events(std::vector<hipEvent_t> &v, size_t n) {
-    while (v.size() < n) {
-        hipEvent_t e;
-        CHR_HIP_CHECK(hipEventCreate(&e));
-        v.push_back(e);
-    }
     return CHR_OK;
 }
 
@@ -5081,21 +5080,20 @@ struct SlotRun {
 // already done by then) to learn when the tail has run -- no survivor-count
 // round trip between steps.  Same launches, same results.  *k_out = slots
 // queued, *ctl_out = their [mode, length] words.
-static int device_slots(const chr_geometry *g, const chr_photons *ph, uint32_t nphotons, uint32_t *rng, uint32_t nslots,
-                        int32_t ntpb, int32_t max_steps, int32_t use_weights, int32_t scatter_first, PropBufs &b,
-                        const SlotRun &run, hipStream_t stream, uint32_t **ctl_out, int *k_out) {
-    const uint32_t tail_below = (uint32_t)ntpb * 16 * 8;   // photon.py:261-264
+static int device_slots(const StepCtx &c, uint32_t nphotons, int32_t ntpb, int32_t max_steps, int32_t scatter_first,
+                        PropBufs &b, const SlotRun &run, uint32_t **ctl_out, int *k_out) {
+    const int32_t use_weights = c.use_weights;
+    hipStream_t stream = c.stream;
+    const uint32_t below = tail_below(ntpb);
     uint32_t *ctl = nullptr;
-    int rc = slot_ctl_get(2 * (size_t)max_steps + 8, &ctl, run.ctx);
+    int rc = slot_ctl_get(max_steps, &ctl, run.ctx);
     if (rc) return rc;
     uint32_t *done = ctl + 2 * (size_t)max_steps;
     if (!run.prefix_done) CHR_HIP_CHECK(hipMemsetAsync(done, 0, 4, stream));
     b.fc.enrol_next = true;
     // live records: the default variant's slots, each photon once (use_weights runs the tail at once)
-    b.live = live_records_enabled() && !use_weights && select_step_variant(g).shade_live && b.fc.live[0];
+    b.live = live_records_enabled() && !use_weights && select_step_variant(c.g).shade_live && b.fc.live[0];
     uint32_t *ring = b.pinned + 64;   // (mode, n) of recent slots, 32 entries (written by each slot's head kernel)
-    // slot k + 1's head runs at the end of slot k's scan (no head dispatch per slot)
-    const bool fold = true;
     std::vector<hipEvent_t> &events = *run.events;
     uint32_t n_ub = nphotons;
     int k = 0, cur = 0;
@@ -5103,7 +5101,7 @@ static int device_slots(const chr_geometry *g, const chr_photons *ph, uint32_t n
     while (k < max_steps && !stop) {
         if ((rc = grow_events(events, SLOT_EVENTS * (size_t)(k + 1)))) return rc;
         hipEvent_t *ev = events.data() + SLOT_EVENTS * (size_t)k;
-        SlotCtl sc{ctl + 2 * (size_t)k, ctl + 2 * (size_t)k + 1, done, nphotons, max_steps - k, tail_below};
+        SlotCtl sc{ctl + 2 * (size_t)k, ctl + 2 * (size_t)k + 1, done, nphotons, max_steps - k, below};
         sc.tail_stream = run.tstream;
         sc.tail_masks = b.tail_masks;
         const int timing = slot_timing();
@@ -5114,10 +5112,9 @@ static int device_slots(const chr_geometry *g, const chr_photons *ph, uint32_t n
         sc.slot = k;
         sc.live = b.live;
         sc.host_ring = ring + 2 * (k % 32);   // written by the slot's head kernel (slot 0 of a batch: its prefix's)
-        sc.fold_head = fold;
-        if (fold && k + 1 < max_steps)
+        if (k + 1 < max_steps)   // slot k + 1's head runs at the end of slot k's scan (no head dispatch per slot)
             sc.next_head = HeadNext{ctl + 2 * (size_t)(k + 1), ctl + 2 * (size_t)(k + 1) + 1, done, nullptr,
-                                    ring + 2 * ((k + 1) % 32), tail_below, nphotons, max_steps - k - 1, use_weights};
+                                    ring + 2 * ((k + 1) % 32), below, nphotons, max_steps - k - 1, use_weights};
         if (k == 0 && run.prefix_done) {
             sc.phase = PHASE_REST;
             sc.prefix_done = run.prefix_done;
@@ -5127,9 +5124,10 @@ static int device_slots(const chr_geometry *g, const chr_photons *ph, uint32_t n
         // ev[2] (before the slot's trace) is always recorded: the host's and the tail
         // stream's sync point for the slot (its head has run); the end-of-slot event ev[4]
         // only with every slot event (CHR_SLOT_TIMING=1), else once after the last slot
-        rc = launch_step(g, ph, rng, nslots, (uint32_t)b.cap, n_ub, b.q[cur] + 1, b.q[cur ^ 1], 1, use_weights,
-                         scatter_first, b.scratch, stream, timing == 2 ? ev[0] : nullptr, timing == 2 ? ev[1] : nullptr,
-                         b.hits, b.sort_space, k == 0, ev[2], timing ? ev[3] : nullptr, &split, &b.fc, &sc);
+        rc = launch_step(c, n_ub, b.q[cur] + 1, b.q[cur ^ 1], 1, scatter_first, k == 0,
+                         StepEvents{timing == 2 ? ev[0] : nullptr, timing == 2 ? ev[1] : nullptr, ev[2],
+                                    timing ? ev[3] : nullptr},
+                         &split, &sc);
         if (rc) return rc;
         if (timing == 2) CHR_HIP_CHECK(hipEventRecord(ev[4], stream));
         cur ^= 1;
@@ -5149,6 +5147,17 @@ static int device_slots(const chr_geometry *g, const chr_photons *ph, uint32_t n
     return CHR_OK;
 }
 
+// one trace launch over `rays` queued photons in the statistics
+static void add_trace_launch(chr_propagate_stats &st, uint64_t rays, float ms) {
+    st.trace_ms += ms;
+    if (st.trace_ms_n < CHR_TRACE_MS_MAX) {
+        st.trace_launch_rays[st.trace_ms_n] = (uint32_t)rays;
+        st.trace_launch_ms[st.trace_ms_n++] = ms;
+    }
+    st.trace_launches++;
+    st.trace_rays += rays;
+}
+
 // per-slot statistics of a finished device-driven propagate (h: [mode, length]
 // per slot); prefixed: slot 0 ran as prefix + rest (chr_propagate_batches)
 static int slot_stats(chr_propagate_stats &st, const uint32_t *h, int k, const std::vector<hipEvent_t> &events,
@@ -5165,13 +5174,7 @@ static int slot_stats(chr_propagate_stats &st, const uint32_t *h, int k, const s
             st.steps_run++;
             if (m == STEP_ONE) {
                 if (timing == 1) CHR_HIP_CHECK(hipEventElapsedTime(&ms, ev[2], ev[3]));
-                st.trace_ms += ms;
-                if (st.trace_ms_n < CHR_TRACE_MS_MAX) {
-                    st.trace_launch_rays[st.trace_ms_n] = nj;
-                    st.trace_launch_ms[st.trace_ms_n++] = ms;
-                }
-                st.trace_launches++;
-                st.trace_rays += nj;
+                add_trace_launch(st, nj, ms);
             } else {
                 st.tail_photons += nj;
             }
@@ -5191,13 +5194,7 @@ static int slot_stats(chr_propagate_stats &st, const uint32_t *h, int k, const s
         st.steps_run++;
         if (m == STEP_ONE) {
             CHR_HIP_CHECK(hipEventElapsedTime(&ms, ev[2], ev[3]));
-            st.trace_ms += ms;
-            if (st.trace_ms_n < CHR_TRACE_MS_MAX) {
-                st.trace_launch_rays[st.trace_ms_n] = nj;
-                st.trace_launch_ms[st.trace_ms_n++] = ms;
-            }
-            st.trace_launches++;
-            st.trace_rays += nj;
+            add_trace_launch(st, nj, ms);
         } else {
             if (tail_stream) {
                 CHR_HIP_CHECK(hipEventElapsedTime(&ms, ev[5], ev[6]));
@@ -5219,12 +5216,11 @@ static int counter_readback(const PropBufs &b, hipStream_t s) {
     return CHR_OK;
 }
 
-static void counter_stats(chr_propagate_stats &st, const PropBufs &b) {
-    const uint32_t *pinned = b.pinned;
+static void counter_stats(chr_propagate_stats &st, const uint32_t *pinned, bool fused) {
     st.stack_overflows = pinned[2];
-    st.flat_walks = b.fused ? pinned[20] : 0u;
-    st.flat_walks_whole = b.fused ? pinned[21] : 0u;
-    if (b.fused) {
+    st.flat_walks = fused ? pinned[20] : 0u;
+    st.flat_walks_whole = fused ? pinned[21] : 0u;
+    if (fused) {
         uint64_t key;
         std::memcpy(&key, pinned + 23, 8);
         st.tail_max_steps = pinned[22];
@@ -5266,9 +5262,113 @@ static int check_propagate_args(const char *fn, const chr_geometry *g, const chr
     return CHR_OK;
 }
 
-static bool device_steps_ok(const chr_geometry *g, const PropBufs &b) {
+static bool device_steps_ok(const chr_geometry *g, bool fused) {
     const StepVariant sv = select_step_variant(g);
-    return b.fused && !trace_steps() && !host_steps_forced() && sv.trace && sv.tail;   // a slot queues both
+    return fused && !trace_steps() && !host_steps_forced() && sv.trace && sv.tail;   // a slot queues both
+}
+
+// Host-driven steps, the reference's loop (photon.py:252-293): per step the launches over the
+// queue -- one launch_step when fused, else a launch_chunk per chunk -- then the survivor count
+// read back from the output queue's header and the other header reset.
+struct HostSteps {
+    int step = 0;         // steps done (a multi-step launch counts every step it was given)
+    int cur = 0;          // the queue the last launches read
+    int64_t n = 0;        // the next queue's length once read back; before that the last launches'
+    // the last step's launches whose events wait for collect_step: after host_steps, those of
+    // the step that reached max_steps (no read-back): the caller drains the stream, then collects
+    size_t pending = 0;
+    bool tail_step = false, split_step = false;   // that step: a multi-step launch; through trace + shade
+    std::vector<hipEvent_t> *events = nullptr;
+};
+// hook(step, queue, n), after the launches of a step and before its read-back: the step's input
+// queue, n entries, written back by the step in stream order
+using StepHook = std::function<int(int, const uint32_t *, uint32_t)>;
+
+// the event times of the pending launches, once the stream has drained
+static int collect_step(chr_propagate_stats &st, HostSteps &h) {
+    const std::vector<hipEvent_t> &events = *h.events;
+    float ms = 0.0f;
+    for (size_t c = 0; c < h.pending; ++c) {
+        CHR_HIP_CHECK(hipEventElapsedTime(&ms, events[2 * c], events[2 * c + 1]));
+        st.kernel_ms += ms;
+        if (h.tail_step) st.tail_ms += ms;
+    }
+    if (h.split_step) {
+        CHR_HIP_CHECK(hipEventElapsedTime(&ms, events[2], events[3]));
+        add_trace_launch(st, (uint64_t)h.n, ms);
+    }
+    h.pending = 0;
+    return CHR_OK;
+}
+
+// one_step: every launch runs one step (tracks); else the nsteps policy of photon.py:261-264.
+// fn: the entry point, for messages.
+static int host_steps(const StepCtx &c, PropBufs &b, uint32_t nphotons, int32_t ntpb, int32_t max_blocks,
+                      int32_t max_steps, int32_t scatter_first, bool one_step, const char *fn, const StepHook *hook,
+                      chr_propagate_stats &st, HostSteps &h) {
+    const uint32_t chunk_cap = (uint32_t)std::min<uint64_t>(b.cap, nphotons);
+    const size_t max_chunks = b.fused ? 2 : (nphotons + chunk_cap - 1) / chunk_cap;   // fused: step + its walk
+    CHR_TRY(timing_events(2 * max_chunks, &h.events));
+    const std::vector<hipEvent_t> &events = *h.events;
+    uint32_t *pinned = b.pinned;
+    b.fc.enrol_next = b.fused;
+    h.n = nphotons;
+    while (h.step < max_steps) {
+        const int64_t n = h.n;
+        const int nsteps = (!one_step && (n < (int64_t)tail_below(ntpb) || c.use_weights)) ? max_steps - h.step : 1;
+        h.tail_step = nsteps > 1;
+        h.split_step = false;
+        if (h.tail_step) st.tail_photons += (uint32_t)n;
+        if (b.fused) {
+            CHR_TRY(launch_step(c, (uint32_t)n, b.q[h.cur] + 1, b.q[h.cur ^ 1], nsteps, scatter_first, h.step == 0,
+                                StepEvents{events[0], events[1], events[2], events[3]}, &h.split_step));
+            st.launches++;
+            h.pending = 1;
+        } else {
+            for (int64_t first = 0; first < n;) {
+                // chunk_iterator (tools.py:159-180)
+                const int64_t left = n - first;
+                int64_t blocks = left / ntpb + (left % ntpb != 0);
+                if (blocks > max_blocks) blocks = max_blocks;
+                const int64_t count = std::min<int64_t>(left, blocks * ntpb);
+                CHR_TRY(launch_chunk(c.g, c.ph, c.rng, c.nslots, (int32_t)first, (int32_t)count, b.q[h.cur] + 1,
+                                     b.q[h.cur ^ 1], nsteps, c.use_weights, scatter_first, b.scratch, c.stream,
+                                     events[2 * h.pending], events[2 * h.pending + 1]));
+                st.launches++;
+                h.pending++;
+                first += count;
+            }
+        }
+        st.steps_run++;
+        h.step += nsteps;
+        scatter_first = 0;
+        if (hook) CHR_TRY((*hook)(h.step, b.q[h.cur] + 1, (uint32_t)n));
+        if (h.step >= max_steps) break;
+        h.cur ^= 1;
+        // read the survivor count (photon.py:284) and reset the other header
+        CHR_HIP_CHECK(hipMemcpyAsync(pinned, b.q[h.cur], 4, hipMemcpyDeviceToHost, c.stream));
+        CHR_HIP_CHECK(hipStreamSynchronize(c.stream));
+        st.host_syncs++;
+        CHR_TRY(collect_step(st, h));
+        h.n = (int64_t)pinned[0] - 1;
+        if (h.n < 0 || h.n > (int64_t)nphotons)
+            return chr::fail(CHR_ERR_INTERNAL, "%s: queue header %u after step %d", fn, pinned[0], h.step);
+        if (trace_steps()) {
+            fprintf(stderr, "%s: step %d nsteps %d -> %lld alive\n", fn, h.step, nsteps, (long long)h.n);
+            if (nsteps == 1 && b.hits) {   // walk-cost histogram of a counting trace variant (zeros otherwise)
+                uint32_t wh[34];
+                CHR_HIP_CHECK(hipMemcpy(wh, b.base + step_layout(b.lay, (uint32_t)n, (uint32_t)n).walk_hist, sizeof(wh),
+                                        hipMemcpyDeviceToHost));
+                fprintf(stderr, "  walk cost (nodes+triangles) log2 histogram:");
+                for (int i = 0; i < 32; ++i) if (wh[i]) fprintf(stderr, " [%u,%u):%u", 1u << i, 2u << i, wh[i]);
+                fprintf(stderr, "\n  worst walk: cost %u photon %u\n", wh[33], wh[32]);
+            }
+        }
+        pinned[1] = 1;
+        CHR_HIP_CHECK(hipMemcpyAsync(b.q[h.cur ^ 1], pinned + 1, 4, hipMemcpyHostToDevice, c.stream));
+        if (h.n == 0) break;
+    }
+    return CHR_OK;
 }
 
 extern "C" int chr_propagate(const chr_geometry *g, const chr_photons *ph, uint32_t nphotons, uint32_t true_nphotons,
@@ -5289,136 +5389,35 @@ extern "C" int chr_propagate(const chr_geometry *g, const chr_photons *ph, uint3
     PropBufs b;
     int rc = prop_bufs(nphotons, ntpb, max_blocks, 0, false, b);
     if (rc) return rc;
-    const uint64_t cap = b.cap;
-    const uint32_t chunk_cap = (uint32_t)std::min<uint64_t>(cap, nphotons);
-    const bool fused = b.fused;
-    uint32_t *const *q = b.q;
-    uint32_t *scratch = b.scratch, *pinned = b.pinned;
-    int2 *hits = b.hits;
-    uint32_t *sort_space = b.sort_space;
-    FlatCtx &fc = b.fc;
+    const StepCtx c = step_ctx(g, ph, d_rng_states, rng_nslots, use_weights, b, stream);
     if ((rc = prop_start(b, nphotons, true_nphotons, ncopies, stream))) return rc;
-    fc.enrol_next = fused;
-    const size_t max_chunks = fused ? 2 : (nphotons + chunk_cap - 1) / chunk_cap;   // fused: step + its walk
-    std::vector<hipEvent_t> *evp = nullptr;
-    if ((rc = timing_events(2 * max_chunks, &evp))) return rc;
-    std::vector<hipEvent_t> &events = *evp;
-    double kernel_ms = 0.0, trace_ms = 0.0;
-    bool split_step = false, tail_step = false;
-    int64_t n_launch = 0;   // queue length of the launch being collected
-    auto collect = [&](size_t nchunks) -> int {
-        for (size_t c = 0; c < nchunks; ++c) {
-            float ms = 0.0f;
-            CHR_HIP_CHECK(hipEventElapsedTime(&ms, events[2 * c], events[2 * c + 1]));
-            kernel_ms += ms;
-            if (tail_step) st.tail_ms += ms;
-        }
-        if (fused && split_step) {
-            float ms = 0.0f;
-            CHR_HIP_CHECK(hipEventElapsedTime(&ms, events[2], events[3]));
-            trace_ms += ms;
-            if (st.trace_ms_n < CHR_TRACE_MS_MAX) {
-                st.trace_launch_rays[st.trace_ms_n] = (uint32_t)n_launch;
-                st.trace_launch_ms[st.trace_ms_n++] = ms;
-            }
-        }
-        return CHR_OK;
-    };
-    int cur = 0;
-    int64_t n = nphotons;
-    int step = 0;
-    const bool device_steps = device_steps_ok(g, b);
-    if (device_steps) {
+    HostSteps h;
+    if (device_steps_ok(g, b.fused)) {
         uint32_t *ctl = nullptr;
         int k = 0;
         SlotRun run;
         if ((rc = timing_events(0, &run.events))) return rc;
-        if ((rc = device_slots(g, ph, nphotons, d_rng_states, rng_nslots, ntpb, max_steps, use_weights, scatter_first,
-                               b, run, stream, &ctl, &k)))
-            return rc;
+        if ((rc = device_slots(c, nphotons, ntpb, max_steps, scatter_first, b, run, &ctl, &k))) return rc;
         CHR_HIP_CHECK(hipStreamSynchronize(stream));
         st.host_syncs = 1;
-        std::vector<uint32_t> h(2 * (size_t)k);
-        CHR_HIP_CHECK(hipMemcpy(h.data(), ctl, 8 * (size_t)k, hipMemcpyDeviceToHost));
-        if ((rc = timing_events(0, &evp))) return rc;
-        if ((rc = slot_stats(st, h.data(), k, *evp, false, b.live))) return rc;
-        step = max_steps;   // as the host loop: it leaves early only on an empty queue
-        n = 0;
-    }
-    while (!device_steps && step < max_steps) {
-        const int nsteps = (n < (int64_t)ntpb * 16 * 8 || use_weights) ? max_steps - step : 1;   // photon.py:261-264
-        const int64_t n_prev = n;
-        n_launch = n;
-        tail_step = nsteps > 1;
-        if (tail_step) st.tail_photons += (uint32_t)n;
-        size_t nchunks = 0;
-        if (fused) {
-            rc = launch_step(g, ph, d_rng_states, rng_nslots, (uint32_t)cap, (uint32_t)n, q[cur] + 1, q[cur ^ 1],
-                             nsteps, use_weights, scatter_first, scratch, stream, events[0], events[1], hits,
-                             sort_space, step == 0, events[2], events[3], &split_step, &fc);
-            if (rc) return rc;
-            st.launches++;
-            nchunks = 1;
-            if (split_step) {
-                st.trace_launches++;
-                st.trace_rays += (uint64_t)n;
-            }
-        } else {
-            int64_t first = 0;
-            while (first < n) {
-                // chunk_iterator (tools.py:159-180)
-                const int64_t left = n - first;
-                int64_t blocks = left / ntpb + (left % ntpb != 0);
-                if (blocks > max_blocks) blocks = max_blocks;
-                const int64_t count = std::min<int64_t>(left, blocks * ntpb);
-                rc = launch_chunk(g, ph, d_rng_states, rng_nslots, (int32_t)first, (int32_t)count, q[cur] + 1,
-                                  q[cur ^ 1], nsteps, use_weights, scatter_first, scratch, stream, events[2 * nchunks],
-                                  events[2 * nchunks + 1]);
-                if (rc) return rc;
-                st.launches++;
-                nchunks++;
-                first += count;
-            }
-        }
-        st.steps_run++;
-        step += nsteps;
-        scatter_first = 0;
-        if (step < max_steps) {
-            cur ^= 1;
-            // read the survivor count (photon.py:284) and reset the other header
-            CHR_HIP_CHECK(hipMemcpyAsync(pinned, q[cur], 4, hipMemcpyDeviceToHost, stream));
+        std::vector<uint32_t> modes(2 * (size_t)k);
+        CHR_HIP_CHECK(hipMemcpy(modes.data(), ctl, 8 * (size_t)k, hipMemcpyDeviceToHost));
+        if ((rc = slot_stats(st, modes.data(), k, *run.events, false, b.live))) return rc;
+        h.step = max_steps;   // as the host loop: it leaves early only on an empty queue
+    } else {
+        if ((rc = host_steps(c, b, nphotons, ntpb, max_blocks, max_steps, scatter_first, false, "chr_propagate", nullptr,
+                             st, h)))
+            return rc;
+        if (h.pending) {   // last step (no survivor read-back): drain before collecting
             CHR_HIP_CHECK(hipStreamSynchronize(stream));
             st.host_syncs++;
-            if ((rc = collect(nchunks))) return rc;
-            nchunks = 0;
-            n = (int64_t)pinned[0] - 1;
-            if (trace_steps()) {
-                fprintf(stderr, "chr_propagate: step %d nsteps %d -> %lld alive\n", step, nsteps, (long long)n);
-                if (nsteps == 1 && hits) {   // walk-cost histogram of a counting trace variant (zeros otherwise)
-                    uint32_t wh[34];
-                    CHR_HIP_CHECK(hipMemcpy(wh, (uint32_t *)(hits + n_prev) + 16 + 2 * (size_t)n_prev, sizeof(wh),
-                                            hipMemcpyDeviceToHost));
-                    fprintf(stderr, "  walk cost (nodes+triangles) log2 histogram:");
-                    for (int b = 0; b < 32; ++b) if (wh[b]) fprintf(stderr, " [%u,%u):%u", 1u << b, 2u << b, wh[b]);
-                    fprintf(stderr, "\n  worst walk: cost %u photon %u\n", wh[33], wh[32]);
-                }
-            }
-            pinned[1] = 1;
-            CHR_HIP_CHECK(hipMemcpyAsync(q[cur ^ 1], pinned + 1, 4, hipMemcpyHostToDevice, stream));
-            if (n == 0) break;
-        }
-        if (nchunks) {   // last step (no survivor read-back): drain before collecting
-            CHR_HIP_CHECK(hipStreamSynchronize(stream));
-            st.host_syncs++;
-            if ((rc = collect(nchunks))) return rc;
+            if ((rc = collect_step(st, h))) return rc;
         }
     }
     if ((rc = counter_readback(b, stream))) return rc;
     CHR_HIP_CHECK(hipStreamSynchronize(stream));
-    counter_stats(st, b);
-    st.kernel_ms += kernel_ms;
-    st.trace_ms += trace_ms;
-    st.final_alive = (step < max_steps) ? (uint32_t)n : 0u;
+    counter_stats(st, b.pinned, b.fused);
+    st.final_alive = (h.step < max_steps) ? (uint32_t)h.n : 0u;
     if (stats) *stats = st;
     return CHR_OK;
 }
@@ -5492,12 +5491,8 @@ extern "C" int chr_propagate_tracked(const chr_geometry *g, const chr_photons *p
     PropBufs b;
     int rc = prop_bufs(nphotons, ntpb, max_blocks, 0, false, b);
     if (rc) return rc;
-    const uint64_t cap = b.cap;
-    const uint32_t chunk_cap = (uint32_t)std::min<uint64_t>(cap, nphotons);
-    const bool fused = b.fused;
-    uint32_t *const *q = b.q;
+    const StepCtx c = step_ctx(g, ph, d_rng_states, rng_nslots, use_weights, b, stream);
     uint32_t *pinned = b.pinned;
-    FlatCtx &fc = b.fc;
     TrackTemp tmp;
     if (hipMalloc((void **)&tmp.len, ((size_t)nphotons + 2) * 4) != hipSuccess) {
         (void)hipGetLastError();
@@ -5508,95 +5503,21 @@ extern "C" int chr_propagate_tracked(const chr_geometry *g, const chr_photons *p
     const uint64_t first_cap = capacity_hint ? capacity_hint : (uint64_t)nphotons * (max_steps >= 1 ? 2u : 1u);
     if ((rc = tracks_reserve(*tr, 0, std::max<uint64_t>(first_cap, nphotons), stream))) return rc;
     if ((rc = prop_start(b, nphotons, true_nphotons, ncopies, stream))) return rc;
-    fc.enrol_next = fused;
     // entry 0: the input state of the first queue
-    if ((rc = chr::tracks_record(ph, q[0] + 1, nphotons, nphotons, 0u, tr->d_step, tmp.len, bad, stream))) return rc;
+    if ((rc = chr::tracks_record(ph, b.q[0] + 1, nphotons, nphotons, 0u, tr->d_step, tmp.len, bad, stream))) return rc;
     uint64_t nrec = nphotons;
-    const size_t max_chunks = fused ? 2 : (nphotons + chunk_cap - 1) / chunk_cap;   // fused: step + its walk
-    std::vector<hipEvent_t> *evp = nullptr;
-    if ((rc = timing_events(2 * max_chunks, &evp))) return rc;
-    std::vector<hipEvent_t> &events = *evp;
-    double kernel_ms = 0.0, trace_ms = 0.0;
-    bool split_step = false;
-    int64_t n_launch = 0;
-    auto collect = [&](size_t nchunks) -> int {
-        for (size_t c = 0; c < nchunks; ++c) {
-            float ms = 0.0f;
-            CHR_HIP_CHECK(hipEventElapsedTime(&ms, events[2 * c], events[2 * c + 1]));
-            kernel_ms += ms;
-        }
-        if (fused && split_step) {
-            float ms = 0.0f;
-            CHR_HIP_CHECK(hipEventElapsedTime(&ms, events[2], events[3]));
-            trace_ms += ms;
-            if (st.trace_ms_n < CHR_TRACE_MS_MAX) {
-                st.trace_launch_rays[st.trace_ms_n] = (uint32_t)n_launch;
-                st.trace_launch_ms[st.trace_ms_n++] = ms;
-            }
-        }
-        return CHR_OK;
-    };
-    int cur = 0;
-    int64_t n = nphotons;
-    int step = 0;
-    size_t nchunks = 0;
-    while (step < max_steps) {
-        n_launch = n;
-        nchunks = 0;
-        if (fused) {
-            rc = launch_step(g, ph, d_rng_states, rng_nslots, (uint32_t)cap, (uint32_t)n, q[cur] + 1, q[cur ^ 1], 1,
-                             use_weights, scatter_first, b.scratch, stream, events[0], events[1], b.hits, b.sort_space,
-                             step == 0, events[2], events[3], &split_step, &fc);
-            if (rc) return rc;
-            st.launches++;
-            nchunks = 1;
-            if (split_step) {
-                st.trace_launches++;
-                st.trace_rays += (uint64_t)n;
-            }
-        } else {
-            int64_t first = 0;
-            while (first < n) {
-                // chunk_iterator (tools.py:159-180)
-                const int64_t left = n - first;
-                int64_t blocks = left / ntpb + (left % ntpb != 0);
-                if (blocks > max_blocks) blocks = max_blocks;
-                const int64_t count = std::min<int64_t>(left, blocks * ntpb);
-                rc = launch_chunk(g, ph, d_rng_states, rng_nslots, (int32_t)first, (int32_t)count, q[cur] + 1,
-                                  q[cur ^ 1], 1, use_weights, scatter_first, b.scratch, stream, events[2 * nchunks],
-                                  events[2 * nchunks + 1]);
-                if (rc) return rc;
-                st.launches++;
-                nchunks++;
-                first += count;
-            }
-        }
-        st.steps_run++;
-        step++;
-        scatter_first = 0;
-        // entry `step`: the step's input queue after its write-back (the host knows its length)
-        if ((rc = tracks_reserve(*tr, nrec, nrec + (uint64_t)n, stream))) return rc;
-        if ((rc = chr::tracks_record(ph, q[cur] + 1, (uint32_t)n, nphotons, (uint32_t)step, tr->d_step + 4 * nrec,
-                                     tmp.len, bad, stream)))
-            return rc;
+    // entry `step`: the step's input queue after its write-back (the host knows its length)
+    const StepHook record = [&](int step, const uint32_t *queue, uint32_t n) -> int {
+        CHR_TRY(tracks_reserve(*tr, nrec, nrec + (uint64_t)n, stream));
+        CHR_TRY(chr::tracks_record(ph, queue, n, nphotons, (uint32_t)step, tr->d_step + 4 * nrec, tmp.len, bad, stream));
         tr->counts.push_back((uint64_t)n);
         nrec += (uint64_t)n;
-        if (step < max_steps) {
-            cur ^= 1;
-            // read the survivor count (photon.py:284) and reset the other header
-            CHR_HIP_CHECK(hipMemcpyAsync(pinned, q[cur], 4, hipMemcpyDeviceToHost, stream));
-            CHR_HIP_CHECK(hipStreamSynchronize(stream));
-            st.host_syncs++;
-            if ((rc = collect(nchunks))) return rc;
-            nchunks = 0;
-            n = (int64_t)pinned[0] - 1;
-            if (n < 0 || n > (int64_t)nphotons)
-                return chr::fail(CHR_ERR_INTERNAL, "chr_propagate_tracked: queue header %u after step %d", pinned[0], step);
-            pinned[1] = 1;
-            CHR_HIP_CHECK(hipMemcpyAsync(q[cur ^ 1], pinned + 1, 4, hipMemcpyHostToDevice, stream));
-            if (n == 0) break;
-        }
-    }
+        return CHR_OK;
+    };
+    HostSteps h;
+    if ((rc = host_steps(c, b, nphotons, ntpb, max_blocks, max_steps, scatter_first, true, "chr_propagate_tracked",
+                         &record, st, h)))
+        return rc;
     // the two orders' offsets, and the photon-major copy
     tr->nrecords = nrec;
     const size_t nentries = tr->counts.size();
@@ -5617,7 +5538,7 @@ extern "C" int chr_propagate_tracked(const chr_geometry *g, const chr_photons *p
     CHR_HIP_CHECK(hipMemcpyAsync(pinned + 42, tr->d_flat_offsets + nphotons, 8, hipMemcpyDeviceToHost, stream));
     CHR_HIP_CHECK(hipStreamSynchronize(stream));
     st.host_syncs++;
-    if (nchunks && (rc = collect(nchunks))) return rc;
+    if (h.pending && (rc = collect_step(st, h))) return rc;
     uint64_t total = 0;
     std::memcpy(&total, pinned + 42, 8);
     if (pinned[40] != 0)
@@ -5626,10 +5547,8 @@ extern "C" int chr_propagate_tracked(const chr_geometry *g, const chr_photons *p
     if (total != nrec)
         return chr::fail(CHR_ERR_INTERNAL, "chr_propagate_tracked: track lengths sum to %llu, %llu records written",
                          (unsigned long long)total, (unsigned long long)nrec);
-    counter_stats(st, b);
-    st.kernel_ms += kernel_ms;
-    st.trace_ms += trace_ms;
-    st.final_alive = max_steps == 0 ? nphotons : ((step < max_steps) ? (uint32_t)n : 0u);
+    counter_stats(st, pinned, b.fused);
+    st.final_alive = max_steps == 0 ? nphotons : ((h.step < max_steps) ? (uint32_t)h.n : 0u);
     if (stats) *stats = st;
     *out = tr.release();
     return CHR_OK;
@@ -5712,27 +5631,24 @@ static bool photons_alias(const chr_photons *a, uint32_t na, const chr_photons *
 // against 425.1 M/s), and the prefix walk on a fraction of the grid (r03 ab4):
 // a walk started beside the running batch's late steps or its tail slows them
 // more than the overlap gains.
-static int queue_prefix(const chr_geometry *g, const chr_photons *ph, uint32_t nphotons, uint32_t true_nphotons,
-                        uint32_t ncopies, uint32_t *rng, uint32_t nslots, int32_t ntpb, int32_t max_steps,
-                        int32_t use_weights, int32_t scatter_first, PropBufs &b, int ctx,
-                        std::vector<hipEvent_t> &events, hipEvent_t prefix_done, hipStream_t ps) {
+static int queue_prefix(const StepCtx &c, uint32_t nphotons, uint32_t true_nphotons, uint32_t ncopies, int32_t ntpb,
+                        int32_t max_steps, int32_t scatter_first, PropBufs &b, int ctx, std::vector<hipEvent_t> &events,
+                        hipEvent_t prefix_done) {
     uint32_t *ctl = nullptr;
-    CHR_TRY(slot_ctl_get(2 * (size_t)max_steps + 8, &ctl, ctx));
+    CHR_TRY(slot_ctl_get(max_steps, &ctl, ctx));
     uint32_t *done = ctl + 2 * (size_t)max_steps;
-    CHR_TRY(prop_start(b, nphotons, true_nphotons, ncopies, ps, done));
+    CHR_TRY(prop_start(b, nphotons, true_nphotons, ncopies, c.stream, done));
     b.fc.enrol_next = true;
     CHR_TRY(grow_events(events, SLOT_EVENTS));
-    SlotCtl sc{ctl, ctl + 1, done, nphotons, max_steps, (uint32_t)ntpb * 16 * 8};
+    SlotCtl sc{ctl, ctl + 1, done, nphotons, max_steps, tail_below(ntpb)};
     sc.phase = PHASE_PREFIX;
     sc.ctx = ctx;
     sc.prefix_done = prefix_done;
     sc.host_ring = b.pinned + 64;   // ring entry 0 (device_slots' slot 0): this head is slot 0's
     hipEvent_t *ev = events.data();
     const int timing = slot_timing();
-    return launch_step(g, ph, rng, nslots, (uint32_t)b.cap, nphotons, b.q[0] + 1, b.q[1], 1, use_weights,
-                       scatter_first, b.scratch, ps, timing == 2 ? ev[0] : nullptr, ev[1], b.hits, b.sort_space, true,
-                       ev[2], timing ? ev[3] : nullptr, nullptr,
-                       &b.fc, &sc);
+    return launch_step(c, nphotons, b.q[0] + 1, b.q[1], 1, scatter_first, true,
+                       StepEvents{timing == 2 ? ev[0] : nullptr, ev[1], ev[2], timing ? ev[3] : nullptr}, nullptr, &sc);
 }
 
 static int propagate_batches(const chr_geometry *g, const chr_photons *phs, const uint32_t *nphotons,
@@ -5759,10 +5675,7 @@ static int propagate_batches(const chr_geometry *g, const chr_photons *phs, cons
         if (nphotons[i]) { idx.push_back(i); max_n = std::max(max_n, nphotons[i]); }
     if (idx.empty()) return CHR_OK;
     if (walks_reference_bvh(g)) CHR_TRY(chr::geometry_ref_nodes(g));
-    PropBufs probe;
-    probe.cap = (uint64_t)ntpb * max_blocks;
-    probe.fused = (probe.cap % 64 == 0) && probe.cap <= 0x7FFFFFFFull && step_launch_enabled();
-    if (idx.size() == 1 || !device_steps_ok(g, probe)) {   // nothing to overlap: one propagate after the other
+    if (idx.size() == 1 || !device_steps_ok(g, fused_ok(ntpb, max_blocks))) {   // nothing to overlap: one propagate after the other
         for (uint32_t i : idx)
             CHR_TRY(chr_propagate(g, phs + i, nphotons[i], true_nphotons[i], ncopies[i], d_rng_states, rng_nslots,
                                   ntpb, max_blocks, max_steps, use_weights, scatter_first, stats ? stats + i : nullptr,
@@ -5781,14 +5694,11 @@ static int propagate_batches(const chr_geometry *g, const chr_photons *phs, cons
     for (int c = 0; c < NCTX && c < (int)nb; ++c) {
         CHR_TRY(prop_bufs(max_n, ntpb, max_blocks, c, true, bufs[c]));
         uint32_t *ctl = nullptr;
-        CHR_TRY(slot_ctl_get(2 * (size_t)max_steps + 8, &ctl, c));
-        const int cus = device_cus();
+        CHR_TRY(slot_ctl_get(max_steps, &ctl, c));
         const StepVariant sv = select_step_variant(g);
-        const uint64_t tb = (uint64_t)sv.trace_block;
-        const uint64_t blocks = std::max<uint64_t>(1, std::min<uint64_t>((uint64_t)cus * 4 * sv.trace_waves * 64 / tb,
-                                                                          ((uint64_t)max_n + tb - 1) / tb));
         uint2 *spill = nullptr;
-        CHR_TRY(walk_stack_get((size_t)WIDE_STACK * blocks * tb * sizeof(uint2), &spill, c));
+        CHR_TRY(pool_get<POOL_WALK_STACK>((size_t)WIDE_STACK * trace_blocks(sv, max_n) * sv.trace_block * sizeof(uint2),
+                                          &spill, c));
     }
     // the photon inputs were written on the caller's stream
     std::vector<hipEvent_t> *entry_ev = nullptr;
@@ -5806,8 +5716,9 @@ static int propagate_batches(const chr_geometry *g, const chr_photons *phs, cons
                 CHR_HIP_CHECK(hipStreamWaitEvent(ps, bh[e].done, 0));
         CHR_TRY(prop_bufs(nphotons[i], ntpb, max_blocks, c, true, bufs[c]));
         bufs[c].pinned = bh[j].pinned;
-        return queue_prefix(g, phs + i, nphotons[i], true_nphotons[i], ncopies[i], d_rng_states, rng_nslots, ntpb,
-                            max_steps, use_weights, scatter_first, bufs[c], c, bh[j].ev, bh[j].prefix_done, ps);
+        return queue_prefix(step_ctx(g, phs + i, d_rng_states, rng_nslots, use_weights, bufs[c], ps), nphotons[i],
+                            true_nphotons[i], ncopies[i], ntpb, max_steps, scatter_first, bufs[c], c, bh[j].ev,
+                            bh[j].prefix_done);
     };
     std::vector<int> slots(nb, 0);
     std::vector<char> live(nb, 0);
@@ -5823,8 +5734,8 @@ static int propagate_batches(const chr_geometry *g, const chr_photons *phs, cons
         run.prefix_done = bh[j].prefix_done;
         run.ctx = c;
         uint32_t *ctl = nullptr;
-        CHR_TRY(device_slots(g, phs + i, nphotons[i], d_rng_states, rng_nslots, ntpb, max_steps, use_weights,
-                             scatter_first, b, run, stream, &ctl, &slots[j]));
+        CHR_TRY(device_slots(step_ctx(g, phs + i, d_rng_states, rng_nslots, use_weights, b, stream), nphotons[i], ntpb,
+                             max_steps, scatter_first, b, run, &ctl, &slots[j]));
         live[j] = b.live;
         // after the batch's last slot (and every tail before it on ts): read its counters back
         CHR_HIP_CHECK(hipStreamWaitEvent(ts, bh[j].ev[SLOT_EVENTS * (size_t)(slots[j] - 1) + 4], 0));
@@ -5837,10 +5748,7 @@ static int propagate_batches(const chr_geometry *g, const chr_photons *phs, cons
     for (size_t j = 0; j < nb; ++j) {
         chr_propagate_stats st{};
         CHR_TRY(slot_stats(st, bh[j].pinned + 128, slots[j], bh[j].ev, true, live[j] != 0, true));
-        PropBufs view;
-        view.fused = true;
-        view.pinned = bh[j].pinned;
-        counter_stats(st, view);
+        counter_stats(st, bh[j].pinned, true);
         st.host_syncs = 1;
         st.final_alive = 0;
         if (stats) stats[idx[j]] = st;
@@ -5873,7 +5781,7 @@ static int select_common(const chr_photons *ph, int32_t start, int32_t n, uint32
     if (mode == 0 && (!solid_map || !s2c)) return chr::fail(CHR_ERR_INVALID, "hits: solid map / channel map missing");
     const uint32_t nwords = (uint32_t)((n + 63) / 64);
     void *buf;
-    int rc = scratch_get((mask_scan_words((uint64_t)n) + 8) * 4 + 64, &buf);
+    int rc = pool_get<POOL_SCRATCH>((mask_scan_words((uint64_t)n) + 8) * 4 + 64, &buf);
     if (rc) return rc;
     uint32_t *cnt = (uint32_t *)buf;
     unsigned long long *masks = (unsigned long long *)((uint32_t *)buf + 8);

@@ -329,21 +329,6 @@ __global__ __launch_bounds__(BLOCK) void process_image_kernel(int nthreads, cons
 
 using namespace chr;
 
-static int render_rank_scratch(size_t bytes, uint32_t **out) {
-    static thread_local Scratch s[16];
-    int dev = 0;
-    CHR_HIP_CHECK(hipGetDevice(&dev));
-    Scratch &x = s[dev & 15];
-    if (x.bytes < bytes) {
-        if (x.ptr) CHR_HIP_CHECK(hipFree(x.ptr));
-        x.ptr = nullptr;
-        CHR_HIP_CHECK(hipMalloc(&x.ptr, bytes));
-        x.bytes = bytes;
-    }
-    *out = (uint32_t *)x.ptr;
-    return CHR_OK;
-}
-
 extern "C" int chr_render(const chr_geometry *g, uint32_t nrays, const float *d_pos, const float *d_dir,
                           const uint32_t *d_colors, uint32_t alpha_depth, uint32_t *d_pixels, float *d_dx,
                           uint32_t *d_dxlen, float *d_color, uint32_t bg_color, void *stream) {
@@ -353,7 +338,7 @@ extern "C" int chr_render(const chr_geometry *g, uint32_t nrays, const float *d_
     if (g->dev.nwnodes == 0) return chr::fail(CHR_ERR_INVALID, "chr_render: the geometry has no traversal BVH");
     if (nrays == 0) return CHR_OK;
     uint32_t *rk = nullptr;
-    if (int rc = render_rank_scratch((size_t)nrays * alpha_depth * 4, &rk)) return rc;
+    if (int rc = pool_get<POOL_RENDER>((size_t)nrays * alpha_depth * 4, &rk)) return rc;
     hipLaunchKernelGGL(render_kernel, dim3(grid_for(nrays)), dim3(BLOCK), 0, (hipStream_t)stream,
                        (const DevGeom *)g->d_dev, nrays, d_pos, d_dir, d_colors, alpha_depth, d_pixels, d_dx, d_dxlen,
                        (float4 *)d_color, bg_color, rk);

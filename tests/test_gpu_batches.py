@@ -254,6 +254,64 @@ def test_switches_identical(cuda, small_detector, monkeypatch, switch, value):
     assert sum(s.trace_launches for s in base[True][2]) > 0
 
 
+@pytest.mark.parametrize('max_steps', [3, 1000])
+def test_step_loop_counters(cuda, small_detector, monkeypatch, max_steps):
+    """One seeded input (20,000 photons, 64 x 256 slots) through the device-driven slots,
+    the host loop with one launch per step (CHR_HOST_STEPS=1), the host loop with one
+    launch per chunk (CHR_STEP_LAUNCH=0) and the tracked host loop: identical photons and
+    RNG states (the tracked loop's where no multi-step launch ran: see below; here 947
+    photons are left after the first step, so the plain drivers end in one), and the
+    counters each driver reports -- the same steps, trace launches,
+    trace rays and tail photons device-driven and host-driven; one stream drain when
+    device-driven, one per step in the plain host loop, and in the tracked loop one per
+    read-back plus the final one (steps_run + 1 when the queue emptied before max_steps,
+    which needs no read-back after its last step, else steps_run)."""
+    from chroma import gpu
+    det = gpu.GPUDetector(small_detector)
+    src = _sources([20000], seed=53)[0]
+
+    def run(env, tracked=False):
+        for k in ('CHR_HOST_STEPS', 'CHR_STEP_LAUNCH'):
+            monkeypatch.delenv(k, raising=False)
+        for k, v in env.items():
+            monkeypatch.setenv(k, v)
+        rng = gpu.get_rng_states(64 * 256, seed=7)
+        gp = _gpu_photons(src)
+        kw = dict(nthreads_per_block=64, max_blocks=256, max_steps=max_steps)
+        if tracked:
+            with gp.propagate_tracks(det, rng, **kw):
+                pass
+        else:
+            gp.propagate(det, rng, **kw)
+        return gp.get(), rng.get(), gp.last_stats
+
+    dev = run({})
+    host = run({'CHR_HOST_STEPS': '1'})
+    chunk = run({'CHR_STEP_LAUNCH': '0'})
+    track = run({}, tracked=True)
+    for label, (_, _, st) in (('default', dev), ('host', host), ('chunk', chunk), ('tracked', track)):
+        print('%s: steps_run %d launches %d trace_launches %d trace_rays %d tail_photons %d host_syncs %d final_alive %d'
+              % (label, st.steps_run, st.launches, st.trace_launches, st.trace_rays, st.tail_photons, st.host_syncs,
+                 st.final_alive))
+    for label, alt in (('CHR_HOST_STEPS=1', host), ('CHR_STEP_LAUNCH=0', chunk)):
+        _same(dev[0], alt[0], label)
+        assert np.array_equal(dev[1], alt[1]), label
+    # the tracked loop runs one step per launch (photon.py:261-264 with track=True), so a photon's
+    # RNG slot is its queue position of that step; a multi-step launch keeps one slot per photon
+    # through all its steps.  The two agree where the plain loop ran no multi-step launch.
+    if host[2].tail_photons == 0:
+        _same(dev[0], track[0], 'propagate_tracks')
+        assert np.array_equal(dev[1], track[1]), 'propagate_tracks'
+    for f in ('steps_run', 'trace_launches', 'trace_rays', 'tail_photons'):
+        assert getattr(dev[2], f) == getattr(host[2], f), f
+    assert dev[2].steps_run >= 1 and dev[2].trace_launches >= 1   # 20,000 >= 64 * 128: the first step is a one-step launch
+    assert dev[2].host_syncs == 1
+    assert host[2].host_syncs == host[2].steps_run
+    assert chunk[2].host_syncs == chunk[2].steps_run
+    emptied = track[2].steps_run < max_steps
+    assert track[2].host_syncs == track[2].steps_run + (1 if emptied else 0)
+
+
 @pytest.mark.parametrize('switch,value', [('CHR_WIDE_LEAF_MAX', '4'), ('CHR_WIDE_LEAF_MAX', '1'),
                                           ('CHR_EXACT_ORDER_ONLY', '1')])
 def test_geometry_build_switches_identical(cuda, small_detector, monkeypatch, switch, value):
