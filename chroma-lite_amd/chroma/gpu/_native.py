@@ -70,6 +70,13 @@ class PhotonsDesc(ctypes.Structure):
                 ('d_weights', c_vp), ('d_flags', c_vp), ('d_last_hit_triangles', c_vp), ('d_evidx', c_vp)]
 
 
+class HitMapDesc(ctypes.Structure):
+    """chr_hitmap_desc: the parameters and arrays of a hit map."""
+    _fields_ = [('nsources', c_u32), ('nchannels', c_i32), ('ntbins', c_u32), ('t_lo', c_f32), ('inv', c_f32),
+                ('d_emitted', c_vp), ('d_counts', c_vp), ('d_tmin', c_vp), ('d_thist', c_vp), ('d_wsum', c_vp),
+                ('d_skipped', c_vp)]
+
+
 class PropagateStats(ctypes.Structure):
     _fields_ = [('steps_run', c_u32), ('launches', c_u32), ('final_alive', c_u32), ('stack_overflows', c_u32),
                 ('kernel_ms', ctypes.c_double), ('nodes_visited', c_u64), ('triangles_tested', c_u64),
@@ -159,6 +166,12 @@ _SIGNATURES = {
     'chr_init_rng_subseq':(c_i32, [c_vp, c_u32, c_u64, c_u64, c_u64, c_vp]),
     'chr_channel_hit_counts': (c_i32, [ctypes.POINTER(PhotonsDesc), c_i32, c_i32, c_u32, c_vp, c_vp, c_vp, c_i32,
                                        c_vp]),
+    'chr_hitmap_clear': (c_i32, [ctypes.POINTER(HitMapDesc), c_vp]),
+    'chr_hitmap_accumulate': (c_i32, [ctypes.POINTER(PhotonsDesc), c_i32, c_i32, c_u32, c_vp, c_vp,
+                                      ctypes.POINTER(HitMapDesc), c_vp]),
+    'chr_hitmap_last_path': (c_i32, []),
+    'chr_hitmap_accumulate_host': (c_i32, [ctypes.POINTER(PhotonsDesc), c_i32, c_i32, c_u32, c_vp, c_vp,
+                                           ctypes.POINTER(HitMapDesc)]),
     'chr_pdf_bin_hits': (c_i32, [c_i32, c_vp, c_vp, c_vp, c_i32, c_f32, c_f32, c_i32, c_f32, c_f32, c_vp, c_vp]),
     'chr_pdf_accumulate_bincount': (c_i32, [c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_f32, c_f32, c_f32, c_i32,
                                             c_vp, c_vp, c_vp]),

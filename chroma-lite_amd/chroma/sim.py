@@ -52,6 +52,25 @@ def daq_event_groups(bounds, nchannels, budget):
     return [(first, min(first + per_group, nevents)) for first in range(0, nevents, per_group)]
 
 
+def hit_map_batches(step_photons, photons_per_batch):
+    """The steps of Simulation.hit_map (their photon counts `step_photons`, in
+    order) in consecutive batches [first, last): a batch closes after the step
+    that brings it to photons_per_batch photons or more, so steps are never
+    split.  Every step is in exactly one batch; a last batch may stay below
+    photons_per_batch (or hold no photon at all)."""
+    counts = np.asarray(step_photons, dtype=np.uint64)
+    need = max(1, int(photons_per_batch))
+    batches, first, held = [], 0, 0
+    for i, n in enumerate(counts.tolist()):
+        held += n
+        if held >= need:
+            batches.append((first, i + 1))
+            first, held = i + 1, 0
+    if first < len(counts):
+        batches.append((first, len(counts)))
+    return batches
+
+
 def _event_tracks_flat(flat, start, end):
     """(offsets, Photons) of the photons [start, end) of a batch's photon-major
     tracks (PhotonTracks.flat()): the event's own offsets, from 0."""
@@ -348,6 +367,55 @@ class Simulation(object):
             yield from flush()
         self.last_pipeline = tuple(stats)
 
+    def hit_map(self, gensteps, nsources, tbins=0, trange=None, earliest=True, weights=False, max_steps=1000,
+                photons_per_batch=1000000, use_weights=False):
+        """The hit map (chroma.gpu.hitmap.HitMap) of the photons of `gensteps`, a
+        Gensteps or an iterable of them: per source and channel the detected
+        photons, the earliest arrival, the arrival-time histogram (tbins bins
+        over trange) and the weight sum.  A step's `evidx` is the caller's
+        absolute source id (0 .. nsources-1; photons of other ids are counted
+        in `skipped`) and is not restamped.  No Event is built and no photon
+        or hit leaves the device: the only downloads are the map and
+        `last_exhausted` (the generator's count, summed over the batches).
+
+        The call sequence, on which the RNG stream depends:
+          records = the steps of all the Gensteps, in order;
+          batches = hit_map_batches(records['nphotons'], photons_per_batch),
+                    those without photons dropped;
+          for each group of up to `pipeline_batches` consecutive batches:
+              made = [chroma.gpu.generate_photons(records[a:b], gpu_geometry, rng_states)
+                      for (a, b) in group]                          # in order
+              chroma.gpu.propagate_batches(made, gpu_geometry, rng_states, nthreads_per_block,
+                                           max_blocks, max_steps, use_weights)
+              GPUHitMap.accumulate(m) for m in made                 # draws nothing
+        """
+        if not hasattr(self.detector, 'num_channels') or self.gpu_geometry.nchannels <= 0:
+            raise ValueError('hit_map needs a detector with channels')
+        from chroma import gensteps as gs
+        parts = [gensteps] if isinstance(gensteps, Gensteps) else list(gensteps)
+        material_objects = getattr(getattr(self.gpu_geometry, 'packed', None), 'material_objects', None)
+        records = [gs._as_records(p, material_objects) for p in parts]
+        records = np.concatenate(records) if records else np.zeros(0, gs.GENSTEP_DTYPE)
+        hm = gpu.GPUHitMap(self.gpu_geometry, nsources, tbins=tbins, trange=trange, earliest=earliest,
+                           weights=weights)
+        cum = np.concatenate([[0], np.cumsum(records['nphotons'].astype(np.uint64))])
+        batches = [(a, b) for a, b in hit_map_batches(records['nphotons'], photons_per_batch) if cum[b] > cum[a]]
+        depth = max(1, int(self.pipeline_batches))
+        self.last_exhausted = 0
+        calls = 0
+        for first in range(0, len(batches), depth):
+            made = [gpu.generate_photons(records[a:b], self.gpu_geometry, self.rng_states)
+                    for a, b in batches[first:first + depth]]
+            self.last_exhausted += sum(m.exhausted for m in made)
+            gpu.propagate_batches(made, self.gpu_geometry, self.rng_states,
+                                  nthreads_per_block=self.nthreads_per_block, max_blocks=self.max_blocks,
+                                  max_steps=max_steps, use_weights=use_weights)
+            calls += 1
+            for m in made:
+                hm.accumulate(m)
+        self.last_pipeline = (len(batches), calls)
+        return hm.get()
+
     def __del__(self):
         ctx = getattr(self, 'context', None)
         if ctx is not None:
@@ -398,6 +466,10 @@ class ShardedSimulation(Simulation):
         # different streams: generate with Simulation (or chroma.gpu.generate_photons from
         # states seeded alike on every rank) and pass the photons
         raise NotImplementedError('Gensteps input is not sharded: generate the photons first')
+
+    def hit_map(self, *args, **kwargs):
+        # the map of a rank's photons would have to be reduced over the ranks (SUM; MIN for tmin)
+        raise NotImplementedError('hit_map is not sharded: use Simulation')
 
     def _upload(self, batch_events):
         from chroma.gpu import shard

@@ -580,6 +580,92 @@ int chr_channel_hit_counts(const chr_photons *ph, int32_t start_photon, int32_t 
                            const int32_t *d_solid_id_to_channel_index, uint32_t *d_counts,
                            int32_t nchannels, void *stream);
 
+/* ---------------------------------------------------------------- hit maps
+ * A hit map is the table "source s flashed N photons: how many reached channel
+ * c, when did the first arrive, how are the arrival times distributed" -- the
+ * optical map (photon library) of fast simulation and reconstruction.  The
+ * source of a photon is its evidx (a genstep's evidx is the caller's absolute
+ * source id; chr_generate_photons stamps it and the propagator leaves it
+ * alone).  No reference counterpart: the reference builds such a table on the
+ * host from one event per source.
+ *
+ * Arrays (device for chr_hitmap_clear / chr_hitmap_accumulate, host for
+ * chr_hitmap_accumulate_host), each of at most 2^31 words:
+ *   d_emitted[nsources]                    u64, required
+ *   d_counts[nsources*nchannels]           u32, required
+ *   d_tmin[nsources*nchannels]             u32, optional (NULL: not kept)
+ *   d_thist[nsources*nchannels*ntbins]     u32, present exactly when ntbins > 0
+ *   d_wsum[nsources*nchannels]             u64, optional (NULL: not kept)
+ *   d_skipped                              one u64 word, required
+ * t_lo and inv describe the time histogram: inv = ntbins / (t_hi - t_lo),
+ * computed once by the caller in float32.
+ *
+ * The rule, for photon p, in this order (csrc/hitmap.h, one text for the
+ * device and the host twin):
+ *   1. s = evidx[p]; s >= nsources: skipped += 1, stop.
+ *   2. emitted[s] += 1, detected or not (the denominator of the visibility).
+ *   3. the channel, as chr_channel_hit_counts selects it: flags[p] &
+ *      detection_state, last_hit[p] > -1, c = s2c[solid_map[last_hit[p]]] with
+ *      0 <= c < nchannels; otherwise stop.
+ *   4. w = s*nchannels + c; counts[w] += 1.
+ *   5. d_tmin kept and t[p] not NaN: tmin[w] = min(tmin[w], key), unsigned,
+ *      key = the order-preserving form of the float's bits b: b ^ 0xFFFFFFFF
+ *      when the sign bit is set, else b ^ 0x80000000 (negative times sort below
+ *      positive ones, unlike the DAQ's raw-bits min).  Cleared word: 0xFFFFFFFF.
+ *   6. ntbins > 0: x = (t[p] - t_lo) * inv, one float32 subtract and one
+ *      float32 multiply, never contracted; x >= 0.0f && x < (float)ntbins:
+ *      thist[w*ntbins + (uint32_t)x] += 1.  NaN and infinite times fail the
+ *      test; there are no under- or overflow bins.
+ *   7. d_wsum kept: wsum[w] += q, q = (uint64_t)(weight[p] * 16777216.0f)
+ *      truncated; 0 for a NaN or negative weight, 2^32 - 1 when the product is
+ *      >= 4294967296.0f.
+ * Every update is an integer add or an unsigned min, so a map is a function of
+ * its photons alone, bit for bit, whatever their order, the path taken or the
+ * split into calls; maps add over calls (SUM; MIN for tmin). */
+typedef struct chr_hitmap_desc {
+    uint32_t nsources;
+    int32_t nchannels;
+    uint32_t ntbins;              /* 0: no time histogram */
+    float t_lo, inv;
+    uint64_t *d_emitted;
+    uint32_t *d_counts, *d_tmin, *d_thist;
+    uint64_t *d_wsum, *d_skipped;
+} chr_hitmap_desc;
+/* words of one source's row the privatised path of chr_hitmap_accumulate keeps in LDS (32 KB) */
+#define CHR_HITMAP_LDS_WORDS 8192
+
+/* Zero every array of the map and set d_tmin to 0xFFFFFFFF.  CHR_ERR_INVALID before
+ * the launch for what chr_hitmap_accumulate refuses of a map.  Async. */
+int chr_hitmap_clear(const chr_hitmap_desc *desc, void *stream);
+/* Add photons [start_photon, start_photon + nphotons) of ph to the map by the rule
+ * above; ph is only read (evidx, flags, last hits; t when d_tmin or d_thist is kept,
+ * weights when d_wsum is).  d_solid_map / d_solid_id_to_channel_index as in
+ * chr_channel_hit_counts.  Two paths with identical words: rule steps 4-7 straight
+ * into global memory, or, when one source's row (nchannels * (1 + [tmin] + ntbins +
+ * 2*[wsum]) words) fits CHR_HITMAP_LDS_WORDS, into an LDS copy of the row of the
+ * workgroup's current source that is swept out when the source changes (the default
+ * then for a map with a time histogram or weight sums, the direct path for counts and
+ * tmin alone; the environment's CHR_HITMAP_PATH=d|l forces one, and l with a row over
+ * the budget falls back to d).  Correctness does not depend on the photons being sorted
+ * by source; the speed does.  CHR_ERR_INVALID before the first launch for: a null
+ * required pointer (ph, its evidx / flags / last hits, its t or weights where read,
+ * the two maps, desc, d_emitted, d_counts, d_skipped); d_thist null while ntbins > 0
+ * or non-null while ntbins == 0; nsources == 0 or nchannels <= 0; an array over 2^31
+ * words; inv not finite or not positive while ntbins > 0; start_photon < 0.
+ * nphotons <= 0 is CHR_OK and touches nothing.  Async on `stream`. */
+int chr_hitmap_accumulate(const chr_photons *ph, int32_t start_photon, int32_t nphotons, uint32_t detection_state,
+                          const uint32_t *d_solid_map, const int32_t *d_solid_id_to_channel_index,
+                          const chr_hitmap_desc *desc, void *stream);
+/* The path of the calling thread's last chr_hitmap_accumulate that launched:
+ * 0 direct, 1 privatised, -1 none yet. */
+int chr_hitmap_last_path(void);
+/* The same on the host (no GPU needed): every pointer of ph, the two maps and desc
+ * addresses HOST memory.  Word-identical to chr_hitmap_accumulate (one source,
+ * csrc/hitmap.h), with the same refusals. */
+int chr_hitmap_accumulate_host(const chr_photons *ph, int32_t start_photon, int32_t nphotons,
+                               uint32_t detection_state, const uint32_t *h_solid_map,
+                               const int32_t *h_solid_id_to_channel_index, const chr_hitmap_desc *desc);
+
 /* ------------------------------------------------------------------- PDF
  * replaces: chroma/cuda/pdf.cu, launched by GPUPDF / GPUKernelPDF
  * (chroma/gpu/pdf.py:7-372).  Inputs are GPUChannels words (t, q: f32; DAQ
