@@ -8,7 +8,15 @@ oracle walks the reference BVH in reference order with searchsorted insertion
 rotated rays.  Transforms bit-exact.  Hybrid: RNG states after the lookup
 pass bit-exact; the lookup sums within 1e-5 relative (float atomic adds on the
 device, id order in the oracle; the reference's atomicExch loop is unordered
-too); the image pass and process_image bit-exact from the same lookups."""
+too); the image pass and process_image bit-exact from the same lookups.
+
+The camera views put no two new hits at one distance into a list (only an
+old and a new one, in the merge: the rotation about z keeps the distance to
+horizontal faces), have no zero direction component, fill every workgroup and
+stay within the LDS half of render_kernel's stack.  The cases of
+render_cases.py (test_render_cases, test_render_cases_repeated,
+test_transforms_ragged) are there for those; test_render_cases.py shows on
+the oracle that each is what it claims."""
 import numpy as np
 import pytest
 
@@ -85,6 +93,117 @@ def test_render_parity(cuda, cube_geometry, small_detector, scene, depth, transp
     want2 = oracle.render(PackedGeometry(geo), pos2, d2, colors, depth, dx=dx0.copy(), dxlen=len0.copy(),
                           color=col0.copy(), bg_color=bg)
     _compare(rays, pix, want2, depth)
+
+
+@pytest.fixture(scope='module')
+def case_scenes(cuda):
+    """render_cases' scenes on the device with the transparent colours:
+    scene -> (packed geometry, GPUGeometry, colours)."""
+    import render_cases as rc
+    from chroma import gpu
+    out = {}
+    for scene, make_scene in (('T', rc.scene_T), ('S', rc.scene_S)):
+        geo = make_scene()
+        colors = _colors(geo, True)
+        saved = geo.colors
+        geo.colors = colors
+        try:
+            gg = gpu.GPUGeometry(geo)
+            gg.colors    # uploaded now, from these colours
+        finally:
+            geo.colors = saved
+        out[scene] = rc.packed(scene), gg, colors
+    return out
+
+
+def _case_depths():
+    import render_cases as rc
+    return rc.CASE_DEPTHS
+
+
+@pytest.mark.parametrize('name,depth', _case_depths())
+def test_render_cases(cuda, case_scenes, name, depth):
+    """Equal-distance entries, flat axes, signed zeros, a zero direction, an
+    origin inside the solids, ragged workgroups and a stack past RENDER_LDS
+    (tests/test_render_cases.py shows each case is what it claims to be)."""
+    import render_cases as rc
+    from chroma import gpu
+    from chroma.gpu import gpuarray as ga
+    scene, _, depths = rc.CASES[name]
+    packed, gg, colors = case_scenes[scene]
+    bg = 0x80FFFFFF if depth == depths[0] else 0
+    pos, d = rc.rays(name)
+    rays = gpu.GPURays(pos, d, max_alpha_depth=10)
+    pix = ga.empty(len(pos), np.uint32)
+    rays.render(gg, pix, alpha_depth=depth, bg_color=bg)
+    want = oracle.render(packed, pos, d, colors, depth, bg_color=bg)
+    assert (want[2] > 0).any() == (name != 'R5')
+    _compare(rays, pix, want, depth)
+
+
+def test_render_cases_repeated(cuda, case_scenes):
+    """R1 three times into the same lists: the same rays again (every distance
+    twice, the new entry before the old one, the longest lists cut at
+    alpha_depth), then rotated rays merged into those."""
+    import render_cases as rc
+    from chroma import gpu
+    from chroma.gpu import gpuarray as ga
+    packed, gg, colors = case_scenes['T']
+    depth, bg = 10, 0x80FFFFFF
+    pos, d = rc.rays('R1')
+    rays = gpu.GPURays(pos, d, max_alpha_depth=10)
+    pix = ga.empty(len(pos), np.uint32)
+    rays.render(gg, pix, alpha_depth=depth, bg_color=bg)
+    want = oracle.render(packed, pos, d, colors, depth, bg_color=bg)
+    _compare(rays, pix, want, depth)
+    rays.render(gg, pix, alpha_depth=depth, keep_last_render=True, bg_color=bg)
+    _, dx1, len1, col1 = want
+    want2 = oracle.render(packed, pos, d, colors, depth, dx=dx1.copy(), dxlen=len1.copy(), color=col1.copy(),
+                          bg_color=bg)
+    first, second = dx1.reshape(-1, depth), want2[1].reshape(-1, depth)
+    for i in np.flatnonzero(len1):
+        assert want2[2][i] == min(depth, 2 * len1[i])
+        assert np.array_equal(second[i, :want2[2][i]], np.repeat(first[i, :len1[i]], 2)[:want2[2][i]])
+    assert (2 * len1 > depth).any()    # some doubled list dropped entries
+    _compare(rays, pix, want2, depth)
+    axis, look = np.array([0.0, 0.0, 1.0], np.float32), (0.0, 0.0, 0.0)
+    rays.rotate_around_point(0.05, axis, look)
+    rays.render(gg, pix, alpha_depth=depth, keep_last_render=True, bg_color=bg)
+    pos3 = oracle.transform(pos, 2, phi=0.05, axis=axis, v=look)
+    d3 = oracle.transform(d, 1, phi=0.05, axis=axis)
+    assert np.array_equal(rays.pos.get().view(np.float32).reshape(-1, 3), pos3)
+    assert np.array_equal(rays.dir.get().view(np.float32).reshape(-1, 3), d3)
+    _, dx2, len2, col2 = want2
+    want3 = oracle.render(packed, pos3, d3, colors, depth, dx=dx2.copy(), dxlen=len2.copy(), color=col2.copy(),
+                          bg_color=bg)
+    _compare(rays, pix, want3, depth)
+
+
+@pytest.mark.parametrize('name', ['R1', 'R2', 'R6'])
+def test_transforms_ragged(cuda, name):
+    """translate, rotate and rotate_around_point on 1500, 325 and 300 rays:
+    the last workgroup of transform_kernel is partly idle."""
+    import render_cases as rc
+    from chroma import gpu
+    pos, d = rc.rays(name)
+    assert len(pos) == {'R1': 1500, 'R2': 325, 'R6': 300}[name]
+    rays = gpu.GPURays(pos, d)
+
+    def check(want_pos, want_dir):
+        assert np.array_equal(rays.pos.get().view(np.float32).reshape(-1, 3).view(np.uint32), want_pos.view(np.uint32))
+        assert np.array_equal(rays.dir.get().view(np.float32).reshape(-1, 3).view(np.uint32), want_dir.view(np.uint32))
+
+    shift, axis, point = (10.0, -5.0, 2.5), (0.0, 0.6, 0.8), (30.0, -40.0, 7.0)
+    rays.translate(shift)
+    want_pos = oracle.transform(pos, 0, v=shift)
+    check(want_pos, d)
+    rays.rotate(0.3, axis)
+    want_pos, want_dir = oracle.transform(want_pos, 1, phi=0.3, axis=axis), oracle.transform(d, 1, phi=0.3, axis=axis)
+    check(want_pos, want_dir)
+    rays.rotate_around_point(-1.1, axis, point)
+    want_pos = oracle.transform(want_pos, 2, phi=-1.1, axis=axis, v=point)
+    want_dir = oracle.transform(want_dir, 1, phi=-1.1, axis=axis)
+    check(want_pos, want_dir)
 
 
 def test_snapshot_and_transforms(cuda, cube_geometry):
