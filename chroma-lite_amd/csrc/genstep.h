@@ -6,7 +6,7 @@
 // op (-ffp-contract=off on both sides), so the two compute the same bits.
 //
 // The few sampling / interpolation helpers it needs are restated here from
-// sampling.h and propagate.hip (which are device-only and stay as they are):
+// sampling.h, photon_state.h and propagate.hip (which are device-only and stay as they are):
 // same operations in the same order, so a generated photon's wavelength and
 // delay are the values the propagator's bulk re-emission would draw from the
 // same uniforms.
@@ -60,7 +60,7 @@ CHR_FN chr_gs_v3 chr_gs_unit(chr_gs_v3 a) {
     return r;
 }
 
-// propagate.hip interp_property (reference geometry.h:61-74)
+// photon_state.h interp_property (reference geometry.h:61-74)
 CHR_FN float chr_gs_interp_property(const chr_gen_tables *tb, float x, const float *fp) {
     const float start = tb->wl_start, step = tb->wl_step;
     const int n = (int)tb->wl_n;

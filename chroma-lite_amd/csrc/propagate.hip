@@ -16,6 +16,10 @@
 //     (the reference's warp-atomic enqueue is nondeterministic);
 //   * all transcendental math is include/chroma_fmath.h, bit-identical to the
 //     CPU oracle.
+//
+// One translation unit ("Source map"): what every section shares, the reference walk and
+// the device profile are in photon_state.h, walk_ref.h and device_profile.h; the sections below
+// follow in the order the source map gives.
 #include <hip/hip_runtime.h>
 #include <rocprim/device/device_radix_sort.hpp>
 
@@ -43,259 +47,12 @@
 #include "tracks.h"
 #include "wide_bvh.h"
 
+// carved headers, in order (make check-headers compiles each one on its own)
+#include "photon_state.h"
+#include "walk_ref.h"
+#include "device_profile.h"
+
 namespace chr {
-
-constexpr int BLOCK = 256;
-constexpr int STACK_SIZE = 1000;   // mesh.h:10
-constexpr int STACK_LDS = 24;      // entries kept in LDS per work-item
-constexpr uint32_t DEAD_MASK = CHR_NO_HIT | CHR_BULK_ABSORB | CHR_SURFACE_DETECT | CHR_SURFACE_ABSORB | CHR_NAN_ABORT;
-constexpr float WEIGHT_LOWER_THRESHOLD = 0.0001f;
-constexpr float SPEED_OF_LIGHT = 299.792458f;
-// float thresholds equivalent to the reference's float-vs-double compares
-// (intersect.h:259-267): (double)u < -1e-6, (double)u > 1+1e-6, (double)t > 1e-6
-constexpr float T_NEG_EPS = -9.99999997e-07f;
-constexpr float T_ONE_EPS = 1.00000095367431640625f;
-constexpr float T_POS_EPS = 9.99999997e-07f;
-
-enum { BREAK = 0, CONTINUE = 1, PASS = 2 };
-
-struct Photon {
-    V3 pos, dir, pol;
-    float wavelength, time, weight;
-    uint32_t history;   // holds a 16-bit value (photon.h:29)
-    int last_hit;
-};
-
-struct State {
-    V3 normal;
-    float n1, n2, absorption_length, scattering_length, distance;
-    int material1, surface_index;
-    bool inside_to_outside;   // photon.h:38 (the hybrid renderer reads it)
-};
-
-#define CHR_LDS __attribute__((address_space(3)))
-#ifndef CHR_COLD
-#define CHR_COLD __forceinline__
-#endif
-// The LDS column pointer travels as a plain value (never inside an object that
-// also holds the scratch spill array: such an object lives in scratch and its
-// LDS pointer degrades to flat loads/stores).
-struct Stack {
-    CHR_LDS uint32_t *lds;   // this work-item's column: entry i at lds[i * BLOCK]
-};
-
-__device__ __forceinline__ void stack_put(const Stack &s, uint32_t *spill, int i, uint32_t v) {
-    if (i < STACK_LDS) s.lds[i * BLOCK] = v;
-    else spill[i - STACK_LDS] = v;
-}
-__device__ __forceinline__ uint32_t stack_get(const Stack &s, const uint32_t *spill, int i) {
-    return (i < STACK_LDS) ? s.lds[i * BLOCK] : spill[i - STACK_LDS];
-}
-
-// Loads through pointers fetched from the device-resident DevGeom are flat
-// (generic) loads unless the address space is stated; flat loads also count in
-// lgkmcnt and so serialise against the LDS stack.  gld() = global_load.
-#define CHR_GLOBAL __attribute__((address_space(1)))
-template <typename T>
-__device__ __forceinline__ T gld(const T *p) { return *(const CHR_GLOBAL T *)p; }
-typedef uint32_t chr_u32x4 __attribute__((ext_vector_type(4)));
-typedef float chr_f32x4 __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ uint4 gld(const uint4 *p) {
-    const chr_u32x4 v = *(const CHR_GLOBAL chr_u32x4 *)p;
-    return make_uint4(v.x, v.y, v.z, v.w);
-}
-__device__ __forceinline__ float4 gld(const float4 *p) {
-    const chr_f32x4 v = *(const CHR_GLOBAL chr_f32x4 *)p;
-    return make_float4(v.x, v.y, v.z, v.w);
-}
-typedef uint32_t chr_u32x2 __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ uint2 gld_lo2(const void *p) {   // the first 8 bytes at p (global_load_dwordx2)
-    const chr_u32x2 v = *(const CHR_GLOBAL chr_u32x2 *)p;
-    return make_uint2(v.x, v.y);
-}
-
-// ---------------------------------------------------------------- geometry.h
-// The top of the wide BVH in LDS (north_star: "BVH nodes ... staged through
-// LDS").  The builder numbers nodes level by level (wide_bvh.cpp), so nodes
-// [0, TOP_NODES) are the root and the two levels below it of the 8-wide tree:
-// every walk starts there and re-enters them from its stack.  A workgroup copies
-// them once (96 B each: the node without its slot pad); a walk reads node i < n
-// from LDS, every other node from global memory.  Same bytes, same results.
-constexpr uint32_t TOP_NODES = 73;   // 1 + 8 + 64: 7,008 B
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));   // (HIP's uint4 has no LDS assignment)
-struct TopNodes {
-    const CHR_LDS u32x4 *p;          // 6 x 16 B per node
-    uint32_t n;                      // nodes held (0: none)
-};
-template <int TB>
-__device__ __forceinline__ TopNodes stage_top(const DevGeom &g, CHR_LDS u32x4 *lds, uint32_t want) {
-    const uint32_t n = want < g.nwnodes ? want : g.nwnodes;   // workgroup-uniform
-    for (uint32_t i = threadIdx.x; i < 6u * n; i += TB) {
-        const uint4 v = gld(g.wnodes + (size_t)g.wstride * (i / 6u) + i % 6u);
-        u32x4 w;
-        w.x = v.x; w.y = v.y; w.z = v.z; w.w = v.w;
-        lds[i] = w;
-    }
-    __syncthreads();
-    return TopNodes{lds, n};
-}
-__device__ __forceinline__ uint4 u4(u32x4 v) { return make_uint4(v.x, v.y, v.z, v.w); }
-__device__ __forceinline__ void load_node(const DevGeom &g, const TopNodes &top, uint32_t node, uint4 &h, uint4 &a1,
-                                          uint4 &a2, uint4 &a3, uint4 &a4, uint4 &a5) {
-    if (node < top.n) {
-        const CHR_LDS u32x4 *tp = top.p + 6u * node;
-        h = u4(tp[0]); a1 = u4(tp[1]); a2 = u4(tp[2]); a3 = u4(tp[3]); a4 = u4(tp[4]); a5 = u4(tp[5]);
-    } else {
-        const uint4 *np = g.wnodes + (size_t)g.wstride * node;
-        h = gld(np); a1 = gld(np + 1); a2 = gld(np + 2); a3 = gld(np + 3); a4 = gld(np + 4); a5 = gld(np + 5);
-    }
-}
-
-__device__ __forceinline__ void node_bounds(const DevGeom &g, uint4 n, V3 &lo, V3 &hi) {
-    lo = v3(__builtin_fmaf((float)(n.x & 0xFFFFu), g.scale, g.ox), __builtin_fmaf((float)(n.y & 0xFFFFu), g.scale, g.oy),
-            __builtin_fmaf((float)(n.z & 0xFFFFu), g.scale, g.oz));
-    hi = v3(__builtin_fmaf((float)(n.x >> 16), g.scale, g.ox), __builtin_fmaf((float)(n.y >> 16), g.scale, g.oy),
-            __builtin_fmaf((float)(n.z >> 16), g.scale, g.oz));
-}
-
-// a table word: from LDS when the tables were copied there (phys_cache), else a global load
-__device__ __forceinline__ float tab(const float *p) {
-    return __builtin_amdgcn_is_shared((const __attribute__((address_space(0))) void *)p) ? *(const CHR_LDS float *)p
-                                                                                         : gld(p);
-}
-__device__ __forceinline__ float interp_property(const DevGeom &g, float x, const float *fp) {
-    const float start = g.wl_start, step = g.wl_step;
-    const int n = (int)g.wl_n;
-    if (x < start) return tab(fp);
-    if (x > __builtin_fmaf((float)(n - 1), step, start)) return tab(fp + n - 1);
-    const int jl = (int)((x - start) / step);
-    const float base = __builtin_fmaf((float)jl, step, start);
-    const float f0 = tab(fp + jl), f1 = tab(fp + jl + 1);
-    return f0 + ((x - base) * (f1 - f0)) / step;
-}
-
-// ---------------------------------------------------------------- intersect.h / mesh.h
-__device__ __forceinline__ bool intersect_box(V3 noid, V3 inv, V3 lo, V3 hi, float &dist) {
-    float tmin = 0.0f, tmax = __builtin_inff();
-    if (chr_isfinite(inv.x)) {
-        const float t0 = __builtin_fmaf(lo.x, inv.x, noid.x), t1 = __builtin_fmaf(hi.x, inv.x, noid.x);
-        tmin = fmax_(tmin, fmin_(t0, t1)); tmax = fmin_(tmax, fmax_(t0, t1));
-    }
-    if (chr_isfinite(inv.y)) {
-        const float t0 = __builtin_fmaf(lo.y, inv.y, noid.y), t1 = __builtin_fmaf(hi.y, inv.y, noid.y);
-        tmin = fmax_(tmin, fmin_(t0, t1)); tmax = fmin_(tmax, fmax_(t0, t1));
-    }
-    if (chr_isfinite(inv.z)) {
-        const float t0 = __builtin_fmaf(lo.z, inv.z, noid.z), t1 = __builtin_fmaf(hi.z, inv.z, noid.z);
-        tmin = fmax_(tmin, fmin_(t0, t1)); tmax = fmin_(tmax, fmax_(t0, t1));
-    }
-    if (tmin > tmax) return false;
-    dist = tmin;
-    return true;
-}
-
-// Moller-Trumbore on a de-indexed record (v0, e1, e2)
-__device__ __forceinline__ bool intersect_triangle(V3 o, V3 d, V3 v0, V3 e1, V3 e2, float &distance) {
-    const V3 h = cross(d, e2);
-    const float a = dot(e1, h);
-    if (a > -1.19209290e-7f && a < 1.19209290e-7f) return false;
-    const float f = 1.0f / a;
-    const V3 s = o - v0;
-    const float u = f * dot(s, h);
-    if (u < T_NEG_EPS || u > T_ONE_EPS) return false;
-    const V3 q = cross(s, e1);
-    const float v = f * dot(d, q);
-    if (v < T_NEG_EPS || u + v > T_ONE_EPS) return false;
-    const float t = f * dot(e2, q);
-    if (t > T_POS_EPS && t < __builtin_inff()) {
-        distance = t;
-        return true;
-    }
-    return false;
-}
-
-// Moller-Trumbore on a wide-BVH triangle record (wide_bvh.h: v0, v1, v2 in
-// r0..r2): the edges v1-v0, v2-v0 are the reference's own float subtractions
-// (intersect.h:26-101), so this is intersect_triangle on the same operands.
-__device__ __forceinline__ bool intersect_record(V3 o, V3 d, float4 r0, float4 r1, float4 r2, float &distance) {
-    const V3 v0 = v3(r0.x, r0.y, r0.z), v1 = v3(r0.w, r1.x, r1.y), v2 = v3(r1.z, r1.w, r2.x);
-    return intersect_triangle(o, d, v0, v1 - v0, v2 - v0, distance);
-}
-// the record index of a wide-BVH triangle record pointer: what the wide walks
-// return for a hit (finish_fill<true> reads the triangle id and normal from it)
-__device__ __forceinline__ int rec_of(const DevGeom &g, const float4 *r) { return (int)((r - g.wtri) >> 2); }
-
-// mesh.h:45-126 -- nearest triangle != last_hit; reference DFS order.
-// The children of a popped group are fetched BATCH at a time (independent
-// 16-byte loads in flight together), their slab tests computed up front, and
-// then walked strictly in index order with the reference's prune / accept /
-// push decisions, so the result (including tie-breaking) is unchanged.
-template <int BATCH>
-__device__ __forceinline__ int intersect_mesh(const DevGeom &g, V3 o, V3 d, float &min_distance, int last_hit,
-                                              Stack st, uint32_t &overflow) {
-    uint32_t spill[STACK_SIZE - STACK_LDS];
-    int triangle_index = -1;
-    min_distance = -1.0f;
-    const V3 noid = v3(-o.x / d.x, -o.y / d.y, -o.z / d.z);
-    const V3 inv = v3(1.0f / d.x, 1.0f / d.y, 1.0f / d.z);
-    const uint4 root = gld(g.nodes);
-    {
-        V3 lo, hi;
-        float bd;
-        node_bounds(g, root, lo, hi);
-        if (!intersect_box(noid, inv, lo, hi, bd)) return -1;
-    }
-    stack_put(st, spill, 0, root.w);
-    int curr = 0;
-    const uint32_t last = (uint32_t)last_hit;
-    while (curr >= 0) {
-        const uint32_t w = stack_get(st, spill, curr);
-        curr--;
-        const uint32_t end = (w & 0x0FFFFFFFu) + (w >> 28);
-        for (uint32_t i = w & 0x0FFFFFFFu; i < end; i += BATCH) {
-            uint4 nd[BATCH];
-#pragma unroll
-            for (int k = 0; k < BATCH; ++k)
-                if (i + k < end) nd[k] = gld(g.nodes + i + k);
-            float bd[BATCH];
-            bool hit[BATCH];
-#pragma unroll
-            for (int k = 0; k < BATCH; ++k) {
-                V3 lo, hi;
-                node_bounds(g, nd[k], lo, hi);
-                hit[k] = (i + k < end) && intersect_box(noid, inv, lo, hi, bd[k]);
-            }
-#pragma unroll
-            for (int k = 0; k < BATCH; ++k) {
-                if (!hit[k]) continue;
-                if (min_distance >= 0.0f && bd[k] > min_distance) continue;
-                const uint32_t child = nd[k].w & 0x0FFFFFFFu;
-                if ((nd[k].w >> 28) == 0) {
-                    if (child != last) {
-                        const float4 *r = g.tri + 3 * (size_t)child;
-                        const float4 r0 = gld(r), r1 = gld(r + 1), r2 = gld(r + 2);
-                        float dist;
-                        if (intersect_triangle(o, d, v3(r0.x, r0.y, r0.z), v3(r0.w, r1.x, r1.y), v3(r1.z, r1.w, r2.x),
-                                               dist)) {
-                            if (triangle_index == -1 || dist < min_distance) {
-                                triangle_index = (int)child;
-                                min_distance = dist;
-                            }
-                        }
-                    }
-                } else {
-                    if (curr + 1 >= STACK_SIZE) {
-                        overflow++;
-                        return triangle_index;
-                    }
-                    curr++;
-                    stack_put(st, spill, curr, nd[k].w);
-                }
-            }
-        }
-    }
-    return triangle_index;
-}
 
 // ---------------------------------------------------------------- wide traversal
 // The same nearest-hit query over the 8-wide SAH BVH (wide_bvh.h).  Each
@@ -446,12 +203,8 @@ __device__ __forceinline__ bool ref_beats(float dx, uint32_t rx, float bdx, floa
 // distance (5.8 mm) in 10 M photons of the 29k bench (oracle.undershoot): the
 // traversal keeps every box entered within 2^-11 (4.9e-4) + 1 mm of
 // max(db, bdb).  (inf stays inf: no best yet.)
-#ifndef CHR_CUT_REL   // (build-time A/B of the margin: -DCHR_CUT_REL=0.0f -DCHR_CUT_ABS=0.0f)
-#define CHR_CUT_REL 0x1p-11f
-#endif
-#ifndef CHR_CUT_ABS
-#define CHR_CUT_ABS 1.0f
-#endif
+constexpr float CHR_CUT_REL = 0x1p-11f;
+constexpr float CHR_CUT_ABS = 1.0f;
 __device__ __forceinline__ float ref_cut(float db, float bdb) {
     const float m = __builtin_fmaxf(db, bdb);
     return __builtin_fmaf(m, CHR_CUT_REL, m + CHR_CUT_ABS);
@@ -599,132 +352,6 @@ __device__ __forceinline__ bool wave_leader() {
     const unsigned long long m = __ballot(1);
     return (unsigned)__lane_id() == (unsigned)(__ffsll((long long)m) - 1);
 }
-
-// ---------------------------------------------------------------- device profile
-// The reference's CHROMA_DEVICE_PROFILE regions (profile.h:9-37: per-call
-// clock64 spans atomically added to per-region counters) for the split step
-// kernels, built only into libchroma_amd_prof.so (-DCHR_DEVICE_PROFILE=1).
-// Instead of two global atomics per call, each work-item keeps its region
-// lane-cycles and calls in registers and a wave adds its sums once at exit.
-// A kernel marks region boundaries with tick(next): the wave time since the
-// last tick goes to the region the work-item was in (a work-item masked off in
-// a branch keeps its region, so the time it waits is charged there).
-#ifdef CHR_DEVICE_PROFILE
-__device__ unsigned long long chr_prof_calls[CHR_PROF_COUNT];
-__device__ unsigned long long chr_prof_cycles[CHR_PROF_COUNT];
-
-// one wave's sum of (calls, cycles) added to region id; every lane of the wave active
-__device__ __forceinline__ void prof_add(int id, unsigned long long calls, unsigned long long cycles) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        calls += __shfl_xor(calls, o);
-        cycles += __shfl_xor(cycles, o);
-    }
-    if (__lane_id() == 0) {
-        if (calls) atomicAdd(&chr_prof_calls[id], calls);
-        if (cycles) atomicAdd(&chr_prof_cycles[id], cycles);
-    }
-}
-template <int N>
-struct Prof {
-    uint32_t cyc[N], calls[N];
-    unsigned long long t, t0;
-    int cur;
-    __device__ __forceinline__ void start(int c) {
-        t0 = t = __builtin_amdgcn_s_memtime();
-        cur = c;
-#pragma unroll
-        for (int i = 0; i < N; ++i) cyc[i] = calls[i] = 0u;
-    }
-    __device__ __forceinline__ void tick(int next) {
-        const unsigned long long now = __builtin_amdgcn_s_memtime();
-        const uint32_t dt = (uint32_t)(now - t);
-        t = now;
-#pragma unroll
-        for (int i = 0; i < N; ++i) cyc[i] += cur == i ? dt : 0u;
-        cur = next;
-    }
-    __device__ __forceinline__ void set(int c) { cur = c; }
-    __device__ __forceinline__ void call(int i, uint32_t k = 1u) { calls[i] += k; }
-    __device__ __forceinline__ unsigned long long total() const { return t - t0; }
-};
-#else
-template <int N>
-struct Prof {
-    __device__ __forceinline__ void start(int) {}
-    __device__ __forceinline__ void tick(int) {}
-    __device__ __forceinline__ void set(int) {}
-    __device__ __forceinline__ void call(int, uint32_t = 1u) {}
-};
-#endif
-
-// Photon watch (profile build only, chr_watch_set / chr_watch_fetch): every step
-// of one photon (its index in one batch's arrays) recorded by the kernel that ran
-// it, in the layout of the oracle's orc_set_watch, so a parity mismatch can be
-// followed step by step on both sides.  Words: kind (1 shade, 2 tail), queue
-// position, hit triangle (-1: none), walk distance, pos in (3), dir in (3), last
-// hit in, material1, absorption length, scattering length, pos out (3), history
-// out, time out, RNG slot.
-#ifdef CHR_DEVICE_PROFILE
-constexpr uint32_t CHR_WATCH_WORDS = 20, CHR_WATCH_MAX = 4096;
-__device__ uint32_t chr_watch_pid = 0xFFFFFFFFu;
-__device__ unsigned long long chr_watch_array = 0ull;   // the batch's pos array (0: any batch)
-__device__ uint32_t chr_watch_n = 0u;
-__device__ uint32_t chr_watch_buf[CHR_WATCH_MAX * CHR_WATCH_WORDS];
-struct Watch {
-    uint32_t w[CHR_WATCH_WORDS];
-    bool on;
-    __device__ __forceinline__ void begin(uint32_t kind, uint32_t pid, const float *pos_array, uint32_t q,
-                                          uint32_t slot, V3 pos, V3 dir, int last_in) {
-        on = chr_watch_pid != 0xFFFFFFFFu && pid == chr_watch_pid && (chr_watch_array == 0ull || chr_watch_array == (unsigned long long)pos_array);
-        if (!on) return;
-        w[0] = kind; w[1] = q; w[19] = slot;
-        w[4] = __float_as_uint(pos.x); w[5] = __float_as_uint(pos.y); w[6] = __float_as_uint(pos.z);
-        w[7] = __float_as_uint(dir.x); w[8] = __float_as_uint(dir.y); w[9] = __float_as_uint(dir.z);
-        w[10] = (uint32_t)last_in;
-    }
-    __device__ __forceinline__ void filled(int tri, const State &s) {
-        if (!on) return;
-        w[2] = (uint32_t)tri; w[3] = __float_as_uint(s.distance); w[11] = (uint32_t)s.material1;
-        w[12] = __float_as_uint(s.absorption_length); w[13] = __float_as_uint(s.scattering_length);
-    }
-    __device__ __forceinline__ void end(V3 pos, uint32_t history, float time) {
-        if (!on) return;
-        w[14] = __float_as_uint(pos.x); w[15] = __float_as_uint(pos.y); w[16] = __float_as_uint(pos.z);
-        w[17] = history; w[18] = __float_as_uint(time);
-        const uint32_t i = atomicAdd(&chr_watch_n, 1u);
-        if (i < CHR_WATCH_MAX)
-            for (uint32_t k = 0; k < CHR_WATCH_WORDS; ++k) chr_watch_buf[i * CHR_WATCH_WORDS + k] = w[k];
-        on = false;
-    }
-};
-// trace_kernel's walk of the watched ray (origin bits chr_wray_o, chr_watch_ray):
-// one 8-word event per step of its lane -- kind, then kind-specific words.
-constexpr uint32_t CHR_WEV_MAX = 8192;
-__device__ uint32_t chr_wray_on = 0u;
-__device__ uint32_t chr_wray_o[3];
-__device__ uint32_t chr_wev_n = 0u;
-__device__ uint32_t chr_wev_buf[CHR_WEV_MAX * 8];
-__device__ __forceinline__ bool wray_match(V3 o) {
-    return chr_wray_on && __float_as_uint(o.x) == chr_wray_o[0] && __float_as_uint(o.y) == chr_wray_o[1] &&
-           __float_as_uint(o.z) == chr_wray_o[2];
-}
-__device__ __forceinline__ void wev(uint32_t k, uint32_t a, uint32_t b, uint32_t c, uint32_t d, uint32_t e,
-                                    uint32_t f, uint32_t h) {
-    const uint32_t i = atomicAdd(&chr_wev_n, 1u);
-    if (i >= CHR_WEV_MAX) return;
-    uint32_t *w = chr_wev_buf + 8 * i;
-    w[0] = k; w[1] = a; w[2] = b; w[3] = c; w[4] = d; w[5] = e; w[6] = f; w[7] = h;
-}
-#define CHR_WEV(on, ...) do { if (on) wev(__VA_ARGS__); } while (0)
-#else
-#define CHR_WEV(on, ...) do { } while (0)
-struct Watch {
-    __device__ __forceinline__ void begin(uint32_t, uint32_t, const float *, uint32_t, uint32_t, V3, V3, int) {}
-    __device__ __forceinline__ void filled(int, const State &) {}
-    __device__ __forceinline__ void end(V3, uint32_t, float) {}
-};
-#endif
 
 // The same query, scheduled for 64-wide SIMT (default).  Leaf triangles are
 // not tested inside the node step of the lane that reached them: a lane that
@@ -1805,15 +1432,10 @@ constexpr uint32_t TAIL_PHYS_WORDS = 8192;     // 32 KB: 2 tail workgroups (+ 40
 // The copy is the launch's dynamic LDS, sized to the geometry's hot words (the
 // demo and 29k detectors: a few KB of their 32 / 48 KB caps), so a workgroup holds
 // only the LDS its geometry needs: host and kernel apply the same rule.
-#ifdef CHR_STATIC_PHYS_LDS   // (build-time A/B: the round-5 static arrays at the caps)
-__host__ __device__ __forceinline__ uint32_t phys_lds_bytes(const DevGeom &, uint32_t) { return 0u; }
-#define CHR_PHYS_LDS(name, cap) __shared__ uint4 name[(cap) / 4]
-#else
 __host__ __device__ __forceinline__ uint32_t phys_lds_bytes(const DevGeom &g, uint32_t cap_words) {
     return g.phys && g.phys_hot_words <= cap_words ? g.phys_hot_words * 4u : 0u;
 }
 #define CHR_PHYS_LDS(name, cap) extern __shared__ uint4 name[]
-#endif
 __device__ __forceinline__ DevGeom phys_cache(const DevGeom &g, uint4 *lds, uint32_t cap_words) {
     DevGeom gl = g;
     if (g.phys && g.phys_hot_words <= cap_words) {   // workgroup-uniform
@@ -2083,39 +1705,6 @@ struct LdsRowsT {
     }
 };
 typedef LdsRowsT<BLOCK> LdsRows;
-
-// Where the lone walker's iteration goes (walk_segment<64>, the tail's
-// long-lived photon; device profile build only): wave-cycles of its stack
-// refill, its fetch (the loads issued and waited for at once, so the expansion
-// after it is compute only), the children's slab tests + near child + pushes +
-// triangle list, and the triangle tests + hit reduction; calls = iterations.
-template <bool ON>
-struct LoneProf {
-    __device__ __forceinline__ void begin() {}
-    __device__ __forceinline__ void tick(int) {}
-    __device__ __forceinline__ void wait_loads() {}
-    __device__ __forceinline__ void flush() {}
-};
-#ifdef CHR_DEVICE_PROFILE
-template <>
-struct LoneProf<true> {
-    unsigned long long cyc[4] = {0ull, 0ull, 0ull, 0ull}, iters = 0ull, t = 0ull;
-    __device__ __forceinline__ void begin() { t = __builtin_amdgcn_s_memtime(); iters++; }
-    __device__ __forceinline__ void tick(int i) {
-        const unsigned long long now = __builtin_amdgcn_s_memtime();
-        cyc[i] += now - t;
-        t = now;
-    }
-    __device__ __forceinline__ void wait_loads() { __builtin_amdgcn_s_waitcnt(0); }
-    __device__ __forceinline__ void flush() {
-        if (__lane_id() == 0) {
-            for (int i = 0; i < 4; ++i) atomicAdd(&chr_prof_cycles[CHR_PROF_LONE_REFILL + i], cyc[i]);
-            atomicAdd(&chr_prof_calls[CHR_PROF_LONE_WALK], iters);
-            atomicAdd(&chr_prof_cycles[CHR_PROF_LONE_WALK], cyc[0] + cyc[1] + cyc[2] + cyc[3]);
-        }
-    }
-};
-#endif
 
 // All 64 lanes call this (converged).  act: the segment has a ray (segment-
 // uniform).  Returns the nearest triangle (-1: none) and its distance in
@@ -3062,45 +2651,6 @@ __device__ __forceinline__ int walk_pair(const DevGeom &g, const TopNodes &top, 
     else lds_st(box + PB_STATE, PS_IDLE);
     return tri;
 }
-
-// Where a long-lived photon's tail step goes (profile build: CHR_PROF_LONG_*):
-// wave cycles per phase of the steps beyond the 64th of each photon, counted by its
-// group's first lane.  mark(i) closes phase i at the current clock.
-enum { LP_WALK, LP_FILL, LP_TO_BOUNDARY, LP_AT_BOUNDARY, LP_OTHER, LP_N };
-template <bool ON>
-struct LongProf {
-    __device__ __forceinline__ void step(bool) {}
-    __device__ __forceinline__ void mark(int) {}
-    __device__ __forceinline__ void flush() {}
-};
-#ifdef CHR_DEVICE_PROFILE
-template <>
-struct LongProf<true> {
-    unsigned long long cyc[LP_N] = {0ull, 0ull, 0ull, 0ull, 0ull}, steps = 0ull, t = 0ull;
-    bool on = false;
-    // a step begins (on: this lane's photon is long and walks this step); the time
-    // since the last phase closed is OTHER (the loop, the ballots, the walk's set-up)
-    __device__ __forceinline__ void step(bool long_walk) {
-        const unsigned long long now = __builtin_amdgcn_s_memtime();
-        if (on) cyc[LP_OTHER] += now - t;
-        on = long_walk;
-        if (on) steps++;
-        t = now;
-    }
-    __device__ __forceinline__ void mark(int i) {
-        const unsigned long long now = __builtin_amdgcn_s_memtime();
-        if (on) cyc[i] += now - t;
-        t = now;
-    }
-    __device__ __forceinline__ void flush() {
-        prof_add(CHR_PROF_LONG_WALK, steps, cyc[LP_WALK]);
-        prof_add(CHR_PROF_LONG_FILL, 0ull, cyc[LP_FILL]);
-        prof_add(CHR_PROF_LONG_TO_BOUNDARY, 0ull, cyc[LP_TO_BOUNDARY]);
-        prof_add(CHR_PROF_LONG_AT_BOUNDARY, 0ull, cyc[LP_AT_BOUNDARY]);
-        prof_add(CHR_PROF_LONG_OTHER, 0ull, cyc[LP_OTHER]);
-    }
-};
-#endif
 
 template <int MINW, bool WIRES = true>
 __global__ __launch_bounds__(BLOCK, MINW) void propagate_tail_kernel(const DevGeom *__restrict__ gdev, PropagateArgs a,
@@ -4379,6 +3929,68 @@ constexpr int BIN_KEY_BITS = 22;
 static_assert(SCAN_WORDS == LAYOUT_SCAN_WORDS && LIVE_QUADS == LAYOUT_LIVE_QUADS, "prop_layout.h: kernel constants");
 extern "C" uint64_t chr_propagate_scratch_words(uint32_t nthreads) { return chunk_scratch_words(nthreads); }
 
+// The run-time switches, each read on every call so that one process can flip them
+// (tests/test_gpu_batches.py test_switches_identical); include/chroma_amd.h lists them.
+
+// CHR_PROPAGATE_VARIANT=<n>: the kernel variant of this call (the table below; default 0)
+static int propagate_variant() {
+    const char *e = getenv("CHR_PROPAGATE_VARIANT");
+    return e ? atoi(e) : 0;
+}
+
+// CHR_PAIR_WALK=0: the tail's lone walks on their own wave only (walk_lone; A/B,
+// default 1: walk_pair with an idle wave of the workgroup as tester)
+static bool pair_walk_enabled() {
+    const char *e = getenv("CHR_PAIR_WALK");
+    return !(e && e[0] == '0');
+}
+// CHR_WALK_UP=0: the tail's walks from the root (A/B; default 1: a walk with a
+// previous hit climbs from that hit's leaf -- walk_lone<true> ahead of the pair walk,
+// and the grouped walks, walk_segment<0, UP>, the lone walk's first iteration taking the
+// start node's ancestors read during the previous step; 2: the lone walks only; 4: as 1
+// without that prefetch -- A/B)
+static uint32_t walk_up_mode() {
+    const char *e = getenv("CHR_WALK_UP");
+    return e && (e[0] == '0' || e[0] == '2' || e[0] == '4') ? (uint32_t)(e[0] - '0') : 1u;
+}
+
+// CHR_LIVE_RECORDS=0: every one-step slot reads and writes the photon arrays (A/B; default:
+// the device-driven slots of the default variant carry live records, shade_kernel's LIVE)
+static bool live_records_enabled() {
+    const char *e = getenv("CHR_LIVE_RECORDS");
+    return !(e && e[0] == '0');
+}
+
+// CHR_SLOT_TIMING: which per-slot timing events a device-driven propagate
+// records.  Each hipEventRecord between two dependent dispatches of a step's
+// chain adds a gap (r03 ab15, 29k bench: all 449.9, trace pair only 452.6,
+// none 454.7 M/s).  Default "trace": only the pair around each trace launch
+// (the stats' trace_ms / trace_launch_ms, which the bench's roofline uses);
+// "1" every slot's events as well (kernel_ms, tail_ms, the prefix split);
+// "0" only the events the streams and the host synchronise on.  Times not
+// recorded read 0 in chr_propagate_stats.
+static int slot_timing() {
+    const char *e = getenv("CHR_SLOT_TIMING");
+    if (!e || e[0] == 't') return 1;
+    if (e[0] == '0') return 0;
+    return 2;
+}
+
+static bool trace_steps() {   // CHR_TRACE_STEPS=1: one stderr line per host step (debugging)
+    const char *e = getenv("CHR_TRACE_STEPS");
+    return e && e[0] == '1';
+}
+
+static bool step_launch_enabled() {   // CHR_STEP_LAUNCH=0: the reference's one-launch-per-chunk structure (A/B)
+    const char *e = getenv("CHR_STEP_LAUNCH");
+    return !(e && e[0] == '0');
+}
+
+static bool host_steps_forced() {     // CHR_HOST_STEPS=1: read the survivor count on the host every step (A/B)
+    const char *e = getenv("CHR_HOST_STEPS");
+    return e && e[0] == '1';
+}
+
 // Kernel variants (CHR_PROPAGATE_VARIANT=<n>, read per launch so one process
 // can A/B them; every variant gives identical results -- tools/ab_variants.py
 // checks histories, last hits and positions).  Measured choices: DESIGN.md
@@ -4417,13 +4029,11 @@ static bool wide_queue_ok(const chr_geometry *g) { return g->dev.nwtri < (1u << 
 
 // whether this call's kernels walk the reference BVH (its nodes must be resident)
 static bool walks_reference_bvh(const chr_geometry *g) {
-    const char *e = getenv("CHR_PROPAGATE_VARIANT");
-    return g->dev.nwnodes == 0 || (e && atoi(e) == kExactVariant);
+    return g->dev.nwnodes == 0 || propagate_variant() == kExactVariant;
 }
 
 static propagate_fn select_variant(const chr_geometry *g) {
-    const char *e = getenv("CHR_PROPAGATE_VARIANT");
-    int v = e ? atoi(e) : 0;
+    int v = propagate_variant();
     if (g->dev.nwnodes == 0) v = kExactVariant;   // no wide BVH for this geometry
     const bool counting = (v == 3 || v == 5 || v == 6);
     if (v == kExactVariant) return propagate_kernel<8, 4, 0>;
@@ -4460,8 +4070,7 @@ static constexpr uint32_t kBinFirstMin = 1u << 20;
 // step (r04 ab3), the walk-order carry (r03 ab10/ab14, r04 ab17: the walk-order scatter
 // cost more than the walks gained), a coherence sort of every launch (r01).
 static StepVariant select_step_variant(const chr_geometry *g) {
-    const char *e = getenv("CHR_PROPAGATE_VARIANT");
-    int v = e ? atoi(e) : 0;
+    int v = propagate_variant();
     const bool wires = g->dev.nwireplanes > 0;   // shade / tail without the wire-plane code otherwise
     StepVariant sv;
     if (g->dev.nwnodes == 0 || v == kExactVariant) {
@@ -4517,8 +4126,6 @@ static StepVariant select_step_variant(const chr_geometry *g) {
 }
 
 // scratch layout (u32 words): [0] overflows [1] queue base [2..11] u64 walk counters [12..15] pad; masks (u64, 8-aligned); offsets
-static bool pair_walk_enabled();
-static uint32_t walk_up_mode();
 struct StepScratch {
     uint32_t *counters;          // [0] overflows, [1] base
     unsigned long long *masks;   // alive bits per queue position
@@ -4615,44 +4222,6 @@ static int flat_get(FlatCtx &fc, int ctx = 0) {
     return pool_get<POOL_FLAT>(256, &fc.ctl, ctx);
 }
 
-static bool trace_steps();
-// CHR_SLOT_TIMING: which per-slot timing events a device-driven propagate
-// records.  Each hipEventRecord between two dependent dispatches of a step's
-// chain adds a gap (r03 ab15, 29k bench: all 449.9, trace pair only 452.6,
-// none 454.7 M/s).  Default "trace": only the pair around each trace launch
-// (the stats' trace_ms / trace_launch_ms, which the bench's roofline uses);
-// "1" every slot's events as well (kernel_ms, tail_ms, the prefix split);
-// "0" only the events the streams and the host synchronise on.  Times not
-// recorded read 0 in chr_propagate_stats.
-// CHR_PAIR_WALK=0: the tail's lone walks on their own wave only (walk_lone; A/B,
-// default 1: walk_pair with an idle wave of the workgroup as tester)
-static bool pair_walk_enabled() {
-    const char *e = getenv("CHR_PAIR_WALK");
-    return !(e && e[0] == '0');
-}
-// CHR_WALK_UP=0: the tail's walks from the root (A/B; default 1: a walk with a
-// previous hit climbs from that hit's leaf -- walk_lone<true> ahead of the pair walk,
-// and the grouped walks, walk_segment<0, UP>, the lone walk's first iteration taking the
-// start node's ancestors read during the previous step; 2: the lone walks only; 4: as 1
-// without that prefetch -- A/B)
-static uint32_t walk_up_mode() {
-    const char *e = getenv("CHR_WALK_UP");
-    return e && (e[0] == '0' || e[0] == '2' || e[0] == '4') ? (uint32_t)(e[0] - '0') : 1u;
-}
-
-// CHR_LIVE_RECORDS=0: every one-step slot reads and writes the photon arrays (A/B; default:
-// the device-driven slots of the default variant carry live records, shade_kernel's LIVE)
-static bool live_records_enabled() {
-    const char *e = getenv("CHR_LIVE_RECORDS");
-    return !(e && e[0] == '0');
-}
-
-static int slot_timing() {
-    const char *e = getenv("CHR_SLOT_TIMING");
-    if (!e || e[0] == 't') return 1;
-    if (e[0] == '0') return 0;
-    return 2;
-}
 // A device-driven step slot (chr_propagate without a host round trip per
 // step): the slot's kernels read the queue length from the input queue's
 // header and run by the mode step_head_kernel picks; n passed to launch_step
@@ -4697,7 +4266,7 @@ constexpr int PHASE_ALL = 0, PHASE_PREFIX = 1, PHASE_REST = 2;
 // (the tail starts below nthreads_per_block * 128 photons and that is at most
 // the slot count; not use_weights, whose tail takes any length).  r03 ab11, 29k
 // bench: 440.4 -> 450.3 M/s (mean tail 6.93 -> 6.65 ms, kernel time per step
-// 29.98 -> 28.37 ms).  CHR_TAIL_WQ=0: one group per slot, as many waves as
+// 29.98 -> 28.37 ms).  Otherwise: one group per slot, as many waves as
 // photons / 8.
 static bool tail_work_queue(const StepVariant &sv, const SlotCtl *sc, int32_t use_weights, uint32_t cap) {
     return sv.tail_group == 8 && sc && !use_weights && sc->tail_below <= cap;
@@ -4970,21 +4539,6 @@ static int timing_events(size_t n, std::vector<hipEvent_t> **out, int ctx = 0) {
     CHR_HIP_CHECK(hipGetDevice(&dev));
     *out = &ev[ctx & 1][dev & 15];
     return grow_events(**out, n);
-}
-
-static bool trace_steps() {   // CHR_TRACE_STEPS=1: one stderr line per host step (debugging)
-    const char *e = getenv("CHR_TRACE_STEPS");
-    return e && e[0] == '1';
-}
-
-static bool step_launch_enabled() {   // CHR_STEP_LAUNCH=0: the reference's one-launch-per-chunk structure (A/B)
-    const char *e = getenv("CHR_STEP_LAUNCH");
-    return !(e && e[0] == '0');
-}
-
-static bool host_steps_forced() {     // CHR_HOST_STEPS=1: read the survivor count on the host every step (A/B)
-    const char *e = getenv("CHR_HOST_STEPS");
-    return e && e[0] == '1';
 }
 
 // per-slot control words of a device-driven propagate: [2k] mode, [2k + 1]
@@ -5873,109 +5427,6 @@ extern "C" int chr_distance_to_mesh(const chr_geometry *g, uint32_t n, const flo
     return CHR_OK;
 }
 
-// Device profile counters (profile.h; profiler.py:217-262 device_fetch / device_reset)
-extern "C" int chr_device_profile_enabled(void) {
-#ifdef CHR_DEVICE_PROFILE
-    return 1;
-#else
-    return 0;
-#endif
-}
-
-extern "C" int chr_device_profile_reset(void *stream) {
-#ifdef CHR_DEVICE_PROFILE
-    void *calls = nullptr, *cycles = nullptr;
-    CHR_HIP_CHECK(hipGetSymbolAddress(&calls, HIP_SYMBOL(chr::chr_prof_calls)));
-    CHR_HIP_CHECK(hipGetSymbolAddress(&cycles, HIP_SYMBOL(chr::chr_prof_cycles)));
-    CHR_HIP_CHECK(hipMemsetAsync(calls, 0, sizeof(unsigned long long) * CHR_PROF_COUNT, (hipStream_t)stream));
-    CHR_HIP_CHECK(hipMemsetAsync(cycles, 0, sizeof(unsigned long long) * CHR_PROF_COUNT, (hipStream_t)stream));
-    return CHR_OK;
-#else
-    (void)stream;
-    return chr::fail(CHR_ERR_INVALID, "device profiling symbols not found: load libchroma_amd_prof.so "
-                                      "(built with -DCHR_DEVICE_PROFILE=1; CHROMA_DEVICE_PROFILE=1)");
-#endif
-}
-
-extern "C" int chr_device_profile_fetch(uint64_t *h_calls, uint64_t *h_cycles, int32_t n, uint32_t *clock_khz) {
-#ifdef CHR_DEVICE_PROFILE
-    if (!h_calls || !h_cycles || n < 0 || n > CHR_PROF_COUNT)
-        return chr::fail(CHR_ERR_INVALID, "device_profile_fetch: bad arguments");
-    CHR_HIP_CHECK(hipDeviceSynchronize());
-    unsigned long long c[CHR_PROF_COUNT], y[CHR_PROF_COUNT];
-    CHR_HIP_CHECK(hipMemcpyFromSymbol(c, HIP_SYMBOL(chr::chr_prof_calls), sizeof(c)));
-    CHR_HIP_CHECK(hipMemcpyFromSymbol(y, HIP_SYMBOL(chr::chr_prof_cycles), sizeof(y)));
-    for (int i = 0; i < n; ++i) { h_calls[i] = c[i]; h_cycles[i] = y[i]; }
-    if (clock_khz) {
-        int dev = 0, khz = 0;
-        CHR_HIP_CHECK(hipGetDevice(&dev));
-        CHR_HIP_CHECK(hipDeviceGetAttribute(&khz, hipDeviceAttributeClockRate, dev));
-        *clock_khz = (uint32_t)khz;
-    }
-    return CHR_OK;
-#else
-    (void)h_calls; (void)h_cycles; (void)n; (void)clock_khz;
-    return chr::fail(CHR_ERR_INVALID, "device profiling symbols not found: load libchroma_amd_prof.so "
-                                      "(built with -DCHR_DEVICE_PROFILE=1; CHROMA_DEVICE_PROFILE=1)");
-#endif
-}
-
-extern "C" int chr_watch_set(uint32_t photon, const float *d_pos_array) {
-#ifdef CHR_DEVICE_PROFILE
-    const unsigned long long arr = (unsigned long long)d_pos_array;
-    const uint32_t zero = 0u;
-    CHR_HIP_CHECK(hipDeviceSynchronize());
-    CHR_HIP_CHECK(hipMemcpyToSymbol(HIP_SYMBOL(chr::chr_watch_pid), &photon, sizeof(photon)));
-    CHR_HIP_CHECK(hipMemcpyToSymbol(HIP_SYMBOL(chr::chr_watch_array), &arr, sizeof(arr)));
-    CHR_HIP_CHECK(hipMemcpyToSymbol(HIP_SYMBOL(chr::chr_watch_n), &zero, sizeof(zero)));
-    return CHR_OK;
-#else
-    (void)photon; (void)d_pos_array;
-    return chr::fail(CHR_ERR_INVALID, "photon watch: load libchroma_amd_prof.so (CHROMA_DEVICE_PROFILE=1)");
-#endif
-}
-
-extern "C" int chr_watch_ray(const float *h_origin, uint32_t *h_events, uint32_t max_events, uint32_t *nevents) {
-#ifdef CHR_DEVICE_PROFILE
-    CHR_HIP_CHECK(hipDeviceSynchronize());
-    if (h_origin) {   // arm: the walk of the ray with this origin (bit-exact) is logged
-        const uint32_t on = 1u, zero = 0u;
-        CHR_HIP_CHECK(hipMemcpyToSymbol(HIP_SYMBOL(chr::chr_wray_o), h_origin, 3 * sizeof(float)));
-        CHR_HIP_CHECK(hipMemcpyToSymbol(HIP_SYMBOL(chr::chr_wev_n), &zero, sizeof(zero)));
-        CHR_HIP_CHECK(hipMemcpyToSymbol(HIP_SYMBOL(chr::chr_wray_on), &on, sizeof(on)));
-        return CHR_OK;
-    }
-    if (!h_events || !nevents) return chr::fail(CHR_ERR_INVALID, "watch_ray: bad arguments");
-    uint32_t n = 0;
-    CHR_HIP_CHECK(hipMemcpyFromSymbol(&n, HIP_SYMBOL(chr::chr_wev_n), sizeof(n)));
-    *nevents = n;
-    uint32_t k = n < max_events ? n : max_events;
-    if (k > chr::CHR_WEV_MAX) k = chr::CHR_WEV_MAX;
-    if (k) CHR_HIP_CHECK(hipMemcpyFromSymbol(h_events, HIP_SYMBOL(chr::chr_wev_buf), sizeof(uint32_t) * 8 * k));
-    return CHR_OK;
-#else
-    (void)h_origin; (void)h_events; (void)max_events; (void)nevents;
-    return chr::fail(CHR_ERR_INVALID, "photon watch: load libchroma_amd_prof.so (CHROMA_DEVICE_PROFILE=1)");
-#endif
-}
-
-extern "C" int chr_watch_fetch(uint32_t *h_out, uint32_t max_records, uint32_t *nrecords) {
-#ifdef CHR_DEVICE_PROFILE
-    if (!h_out || !nrecords) return chr::fail(CHR_ERR_INVALID, "watch_fetch: bad arguments");
-    CHR_HIP_CHECK(hipDeviceSynchronize());
-    uint32_t n = 0;
-    CHR_HIP_CHECK(hipMemcpyFromSymbol(&n, HIP_SYMBOL(chr::chr_watch_n), sizeof(n)));
-    *nrecords = n;
-    uint32_t k = n < max_records ? n : max_records;
-    if (k > chr::CHR_WATCH_MAX) k = chr::CHR_WATCH_MAX;
-    if (k) CHR_HIP_CHECK(hipMemcpyFromSymbol(h_out, HIP_SYMBOL(chr::chr_watch_buf), sizeof(uint32_t) * k * chr::CHR_WATCH_WORDS));
-    return CHR_OK;
-#else
-    (void)h_out; (void)max_records; (void)nrecords;
-    return chr::fail(CHR_ERR_INVALID, "photon watch: load libchroma_amd_prof.so (CHROMA_DEVICE_PROFILE=1)");
-#endif
-}
-
 namespace chr {
 // chr_walk_lone_timing: walk_lone on one wave per workgroup (walker 0), or the
 // pair walk on two (walker 1: wave 0 walks, wave 1 tests), each ray reps times;
@@ -6090,25 +5541,3 @@ extern "C" int chr_walk_lone_timing(const chr_geometry *g, const float *d_rays, 
 // The renderer (render.cu, hybrid_render.cu, transform.cu): same translation
 // unit, it walks the same BVH and runs the same photon physics.
 #include "render.hip"
-
-#ifdef CHR_WALK_PROBE
-// ISA inspection only (make probe): walk_segment alone, whole wave, GS = 64 / run-time width
-namespace chr {
-__global__ __launch_bounds__(BLOCK) void walk_probe_kernel(const DevGeom *__restrict__ gdev, const float *od,
-                                                           int *out, int gs) {
-    __shared__ uint32_t stacks[(BLOCK / 8) * TAIL_STACK * 2];
-    __shared__ uint32_t tris[(BLOCK / 64) * 2 * TAIL_TRI];
-    CHR_LDS uint32_t *wstack = (CHR_LDS uint32_t *)stacks + (threadIdx.x >> 6) * 8 * TAIL_STACK * 2;
-    CHR_LDS uint32_t *wtris = (CHR_LDS uint32_t *)tris + (threadIdx.x >> 6) * 2 * TAIL_TRI;
-    uint32_t overflow = 0, it = 0;
-    float sd;
-    const V3 o = v3(od[0], od[1], od[2]), d = v3(od[3], od[4], od[5]);
-    const TopNodes top{nullptr, 0u};
-    const int st = gs == 64 ? walk_segment<64>(*gdev, true, o, d, 7u, 64, LdsFlat{wstack}, TAIL_STACK * 8, LdsFlat{wtris},
-                                               top, overflow, sd, it)
-                            : walk_segment<0>(*gdev, true, o, d, 7u, gs, LdsFlat{wstack}, TAIL_STACK * gs / 8,
-                                              LdsFlat{wtris}, top, overflow, sd, it);
-    out[threadIdx.x] = st + (int)overflow + (int)it + (int)sd;
-}
-}  // namespace chr
-#endif

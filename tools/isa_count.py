@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Instruction mix of the kernels in a device assembly file (make asm):
-usage: tools/isa_count.py chroma-lite_amd/csrc/_build/propagate.s [name-substring]"""
+usage: tools/isa_count.py chroma-lite_amd/csrc/_build/propagate.s (or propagate_prof.s) [name-substring]"""
 import re
 import sys
 from collections import Counter
