@@ -163,6 +163,8 @@ _SIGNATURES = {
     'chr_daq_end': (c_i32, [c_vp, c_vp, c_vp, c_vp, c_u32, c_i32, c_f32, c_vp]),
     'chr_daq_acquire_events': (c_i32, [ctypes.POINTER(PhotonsDesc), c_i32, c_vp, c_i32, c_vp, c_u32, c_u32, c_vp,
                                        c_vp, c_vp, c_vp, c_vp, c_vp, c_f32, c_i32, c_i32, c_vp]),
+    'chr_daq_acquire_events_many': (c_i32, [ctypes.POINTER(PhotonsDesc), c_i32, c_vp, c_i32, c_vp, c_u32, c_vp, c_u32,
+                                            c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_f32, c_i32, c_i32, c_vp]),
     'chr_init_rng_subseq':(c_i32, [c_vp, c_u32, c_u64, c_u64, c_u64, c_vp]),
     'chr_channel_hit_counts': (c_i32, [ctypes.POINTER(PhotonsDesc), c_i32, c_i32, c_u32, c_vp, c_vp, c_vp, c_i32,
                                        c_vp]),
@@ -173,6 +175,8 @@ _SIGNATURES = {
     'chr_hitmap_accumulate_host': (c_i32, [ctypes.POINTER(PhotonsDesc), c_i32, c_i32, c_u32, c_vp, c_vp,
                                            ctypes.POINTER(HitMapDesc)]),
     'chr_pdf_bin_hits': (c_i32, [c_i32, c_vp, c_vp, c_vp, c_i32, c_f32, c_f32, c_i32, c_f32, c_f32, c_vp, c_vp]),
+    'chr_pdf_bin_hits_rows': (c_i32, [c_i32, c_i32, c_vp, c_vp, c_vp, c_i32, c_f32, c_f32, c_i32, c_f32, c_f32, c_vp,
+                                      c_vp]),
     'chr_pdf_accumulate_bincount': (c_i32, [c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_f32, c_f32, c_f32, c_i32,
                                             c_vp, c_vp, c_vp]),
     'chr_pdf_accumulate_nearest': (c_i32, [c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_vp]),

@@ -4,8 +4,9 @@ The DAQ turns detected photons into per-channel readout: earliest time
 (photon time + a sample of the detector's time CDF), integrated charge (a
 sample of the charge CDF, quantised by charge_unit) and the OR of the photon
 histories.  Kernels: csrc/daq.hip through the C ABI (chr_daq_begin /
-chr_daq_acquire / chr_daq_end, and chr_daq_acquire_events for all events of a
-batch in one call); no host fallback.
+chr_daq_acquire / chr_daq_end, and chr_daq_acquire_events /
+chr_daq_acquire_events_many for all events of a batch in one call); no host
+fallback.
 """
 import ctypes
 
@@ -77,6 +78,12 @@ class GPUEventChannels(object):
             out.append(event.Channels(t < 1e8, t, rows[1, e].view(np.float32).copy(),
                                       rows[2, e].view(np.uint32).copy()))
         return out
+
+    def as_channels(self):
+        """The rows as one GPUChannels of nevents copies of nchannels words (no
+        copy, nothing downloaded): t is the f32 view of the time words."""
+        t = ga.from_tensor(self.time_int.tensor.view(torch.float32), np.float32)
+        return GPUChannels(t, self.q, self.flags, self.nevents, self.nchannels)
 
     def __len__(self):
         return self.nevents
@@ -166,7 +173,8 @@ class GPUDaq(object):
         after another, in one native call whose launches do not depend on the
         number of events (chr_daq_acquire_events): the same channel words and
         the same rng_states afterwards, bit for bit.  Returns a GPUEventChannels
-        of len(bounds) - 1 rows.  ndaq > 1 (run_daq_many) is not batched."""
+        of len(bounds) - 1 rows.  ndaq > 1 (run_daq_many) is not batched here:
+        acquire_events_many is its counterpart."""
         if self.ndaq != 1:
             raise ValueError('acquire_events runs ndaq = 1 acquisitions only (this GPUDaq has ndaq = %d)' % self.ndaq)
         bounds = np.ascontiguousarray(bounds, dtype=np.int64)
@@ -182,3 +190,32 @@ class GPUDaq(object):
                      ctypes.byref(self._desc), t_int.gpudata, q_int.gpudata, hist.gpudata, q.gpudata,
                      ctypes.c_float(weight), int(nthreads_per_block), int(max_blocks), current_stream())
         return GPUEventChannels(t_int, q_int, hist, q, nevents, self.nchannels, host=self._event_host_words)
+
+    def acquire_events_many(self, gpuphotons, rng_states, bounds, nthreads_per_block=64, max_blocks=1024, weight=1.0):
+        """acquire_events for ndaq > 1 (run_daq_many, daq.py:62-91): begin_acquire
+        / acquire / end_acquire for every event [bounds[e], bounds[e+1]) of
+        `gpuphotons` in one native call (chr_daq_acquire_events_many), with the
+        same channel words, rng_states and normal cache afterwards, bit for
+        bit.  Returns GPUChannels of nevents * ndaq copies of nchannels words:
+        event e's copy i is copy e*ndaq + i, so the rows of all events stack as
+        one acquisition of that many copies (GPUPDF.accumulate_pdf_eval takes
+        them as such).  t is the f32 view of the earliest-time words; q holds
+        what end_acquire leaves (copy 0 of every event converted, the others 0).
+        The arrays are views of arrays this GPUDaq reuses: valid until its next
+        acquire_events_many or acquire_events."""
+        if self.ndaq < 2:
+            raise ValueError('acquire_events_many runs ndaq > 1 acquisitions only (acquire_events runs ndaq = 1)')
+        bounds = np.ascontiguousarray(bounds, dtype=np.int64)
+        if bounds.ndim != 1 or len(bounds) < 1:
+            raise ValueError('bounds must be a 1-D array of nevents + 1 photon offsets')
+        nevents = len(bounds) - 1
+        t_int, q_int, hist, q = self._event_arrays(nevents * self.ndaq * self.nchannels)
+        if nevents:
+            ph = gpuphotons._desc()
+            _native.call('chr_daq_acquire_events_many', ctypes.byref(ph), len(gpuphotons.pos), bounds.ctypes.data,
+                         nevents, rng_states.gpudata, len(rng_states), rng_states.normal_cache.gpudata, 0x1 << 2,
+                         self.solid_id_map_gpu.gpudata, ctypes.byref(self._desc), t_int.gpudata, q_int.gpudata,
+                         hist.gpudata, q.gpudata, int(self.ndaq), ctypes.c_float(weight), int(nthreads_per_block),
+                         int(max_blocks), current_stream())
+        t = ga.from_tensor(t_int.tensor.view(torch.float32), np.float32)
+        return GPUChannels(t, q, hist, nevents * self.ndaq, self.nchannels)

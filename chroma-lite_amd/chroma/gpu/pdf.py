@@ -141,6 +141,20 @@ class GPUPDF(object):
                      self.pdf_gpu.gpudata, current_stream())
         self.events_in_histogram += 1
 
+    def add_rows_to_pdf(self, gpuchannels, nthreads_per_block=64):
+        """add_hits_to_pdf for each of the gpuchannels.ndaq consecutive rows of
+        nchannels words (GPUEventChannels.as_channels(): one row per event), in
+        order, in one launch (chr_pdf_bin_hits_rows): the same histogram."""
+        n = len(self.hitcount_gpu)
+        nrows = int(gpuchannels.ndaq)
+        t, q = _channel_words(gpuchannels, n * nrows)
+        if int(gpuchannels.stride) != n:
+            raise ValueError('rows of %d words, %d channels expected' % (gpuchannels.stride, n))
+        _native.call('chr_pdf_bin_hits_rows', n, nrows, q, t, self.hitcount_gpu.gpudata, int(self.tbins),
+                     _f(self.trange[0]), _f(self.trange[1]), int(self.qbins), _f(self.qrange[0]), _f(self.qrange[1]),
+                     self.pdf_gpu.gpudata, current_stream())
+        self.events_in_histogram += nrows
+
     def get_pdfs(self):
         """(hitcount[nchannels], pdf[nchannels, tbins, qbins])"""
         return self.hitcount_gpu.get(), self.pdf_gpu.get().reshape(-1, self.tbins, self.qbins)

@@ -52,6 +52,16 @@ def daq_event_groups(bounds, nchannels, budget):
     return [(first, min(first + per_group, nevents)) for first in range(0, nevents, per_group)]
 
 
+def pdf_copy_groups(nreps, ndaq, nchannels, budget):
+    """The nreps photon copies of one eval_pdf / create_pdf source in consecutive
+    groups [first, last) for GPUDaq.acquire_events_many (acquire_events when
+    ndaq = 1): as many copies per group as fit `budget` bytes of channel rows
+    (four 4-byte words per channel, DAQ copy and photon copy), at least one.
+    Every copy is in exactly one group, in order."""
+    per_group = max(1, int(budget) // (16 * int(ndaq) * int(nchannels)))
+    return [(first, min(first + per_group, int(nreps))) for first in range(0, int(nreps), per_group)]
+
+
 def hit_map_batches(step_photons, photons_per_batch):
     """The steps of Simulation.hit_map (their photon counts `step_photons`, in
     order) in consecutive batches [first, last): a batch closes after the step
@@ -118,6 +128,15 @@ class Simulation(object):
     # reference's list).  False leaves it None for callers who read only
     # ev.photon_tracks_flat = (offsets, Photons), the same records back to back.
     photon_track_lists = True
+    # eval_pdf / create_pdf: the DAQ of a source's photon copies in groups of one native
+    # call each (GPUDaq.acquire_events_many, or acquire_events for ndaq = 1; groups by
+    # pdf_copy_groups under daq_group_bytes) and one accumulation over a group's stacked
+    # rows; accumulators, rng_states and the normal cache bit-identical to the per-copy
+    # loop (tests/test_gpu_pdf_eval.py).  False = that loop: begin / acquire / end /
+    # accumulate per copy.
+    pdf_rows = True
+    # groups of fewer copies than this take the per-copy loop (DESIGN, "Event likelihoods")
+    pdf_rows_min_group = 2
 
     def __init__(self, detector, seed=None, cuda_device=None, photon_tracking=False, nthreads_per_block=512,
                  max_blocks=1024):
@@ -416,6 +435,161 @@ class Simulation(object):
         self.last_pipeline = (len(batches), calls)
         return hm.get()
 
+    # ------------------------------------------------------------ likelihood support
+    def _pdf_sources(self, iterable):
+        """The photon sources of eval_pdf / create_pdf / setup_kernel / eval_kernel,
+        in order: event.Photons as they are, an event.Event's photons_beg, the
+        photons of a Gensteps drawn with self.generate (as simulate does)."""
+        if isinstance(iterable, (event.Photons, event.Event, Gensteps)):
+            iterable = [iterable]
+        for x in iterable:
+            if isinstance(x, event.Vertex):
+                raise NotImplementedError('Vertex input not supported in Chroma')
+            if isinstance(x, Gensteps):
+                yield self.generate(x)
+            elif isinstance(x, event.Event):
+                yield x.photons_beg
+            else:
+                yield x
+
+    def _pdf_daq(self, ndaq):
+        """The GPUDaq of `ndaq` copies (kept: its arrays are reused from call to call)."""
+        if not hasattr(self.detector, 'num_channels') or self.gpu_geometry.nchannels <= 0:
+            raise ValueError('the likelihood methods need a detector with channels')
+        ndaq = int(ndaq)
+        if ndaq < 1:
+            raise ValueError('ndaq must be at least 1')
+        if ndaq == 1:
+            return self.gpu_daq
+        daqs = self.__dict__.setdefault('_pdf_daqs', {})
+        if ndaq not in daqs:
+            daqs[ndaq] = gpu.GPUDaq(self.gpu_geometry, ndaq)
+        return daqs[ndaq]
+
+    def _pdf_copies(self, iterable, nreps, max_steps, use_weights=False):
+        """Per source: (GPUPhotons of nreps propagated copies, photons per copy)."""
+        for source in self._pdf_sources(iterable):
+            gp = gpu.GPUPhotons(source, ncopies=nreps)
+            n = len(gp.pos) // nreps
+            gp.propagate(self.gpu_geometry, self.rng_states, nthreads_per_block=self.nthreads_per_block,
+                         max_blocks=self.max_blocks, max_steps=max_steps, use_weights=use_weights)
+            yield gp, n
+
+    def _acquire_copy(self, daq, gp, c, n):
+        """begin / acquire / end for copy c of gp's n-photon copies."""
+        daq.begin_acquire()
+        daq.acquire(gp, self.rng_states, nthreads_per_block=self.nthreads_per_block, max_blocks=self.max_blocks,
+                    start_photon=c * n, nphotons=n)
+        return daq.end_acquire()
+
+    def _acquire_copy_rows(self, daq, gp, n, nreps, accumulate, accumulate_rows):
+        """The DAQ of all nreps copies of gp, copy by copy (pdf_rows False, and
+        groups below pdf_rows_min_group) or a group per native call, each
+        acquisition handed to accumulate / each group's stacked rows to
+        accumulate_rows.  No row is downloaded."""
+        kw = dict(nthreads_per_block=self.nthreads_per_block, max_blocks=self.max_blocks)
+        if not self.pdf_rows:
+            groups = [(0, nreps)]
+        else:
+            groups = pdf_copy_groups(nreps, daq.ndaq, daq.nchannels, self.daq_group_bytes)
+        for first, last in groups:
+            if not self.pdf_rows or last - first < self.pdf_rows_min_group:
+                for c in range(first, last):
+                    accumulate(self._acquire_copy(daq, gp, c, n))
+                continue
+            bounds = np.arange(first, last + 1, dtype=np.int64) * n
+            if daq.ndaq == 1:
+                rows = daq.acquire_events(gp, self.rng_states, bounds, **kw).as_channels()
+            else:
+                rows = daq.acquire_events_many(gp, self.rng_states, bounds, **kw)
+            accumulate_rows(rows)
+
+    def eval_pdf(self, event_channels, iterable, min_twidth, trange, min_qwidth, qrange, min_bin_content=100,
+                 nreps=1, ndaq=1, time_only=True, max_steps=100, use_weights=False):
+        """The adaptive-bin PDF of `iterable`'s sources (event.Photons, Events with
+        photons_beg, or Gensteps) evaluated at the observed event_channels:
+        (hitcount, pdf_value, pdf_uncert) per channel (GPUPDF.get_pdf_eval).
+        Every source is propagated nreps times and every propagated copy read
+        out by ndaq DAQ copies, so a channel's hitcount is out of
+        nsources * nreps * ndaq.
+
+        The call sequence, on which the RNG stream depends:
+          gpu_pdf.setup_pdf_eval(hit, t, q, min_twidth, trange, min_qwidth, qrange, min_bin_content,
+                                 time_only); gpu_pdf.clear_pdf_eval()
+          daq = GPUDaq(gpu_geometry, ndaq)                       # kept per ndaq
+          for each source, n photons:
+              gp = GPUPhotons(source, ncopies=nreps)
+              gp.propagate(gpu_geometry, rng_states, nthreads_per_block, max_blocks,
+                           max_steps=max_steps, use_weights=use_weights)
+              for c in range(nreps):
+                  daq.begin_acquire()
+                  daq.acquire(gp, rng_states, nthreads_per_block, max_blocks, start_photon=c*n, nphotons=n)
+                  gpu_pdf.accumulate_pdf_eval(daq.end_acquire())
+          return gpu_pdf.get_pdf_eval()
+        With pdf_rows the copies of a source are taken in the groups of
+        pdf_copy_groups(nreps, ndaq, nchannels, daq_group_bytes): one
+        GPUDaq.acquire_events_many (acquire_events for ndaq = 1) and one
+        accumulate_pdf_eval over the group's stacked rows per group, with the
+        same accumulator words, rng_states and normal cache."""
+        daq = self._pdf_daq(ndaq)
+        pdf = self.gpu_pdf
+        pdf.setup_pdf_eval(event_channels.hit, event_channels.t, event_channels.q, min_twidth, trange, min_qwidth,
+                           qrange, min_bin_content=min_bin_content, time_only=time_only)
+        pdf.clear_pdf_eval()
+        for gp, n in self._pdf_copies(iterable, nreps, max_steps, use_weights):
+            self._acquire_copy_rows(daq, gp, n, nreps, pdf.accumulate_pdf_eval, pdf.accumulate_pdf_eval)
+        return pdf.get_pdf_eval()
+
+    def create_pdf(self, iterable, tbins, trange, qbins, qrange, nreps=1, max_steps=100):
+        """The [channel, time bin, charge bin] histogram of `iterable`'s sources,
+        every source propagated nreps times and every copy read out by one
+        DAQ: (hitcount, pdf) (GPUPDF.get_pdfs).  eval_pdf's sequence with ndaq =
+        1 and gpu_pdf.add_hits_to_pdf in place of the accumulation (with
+        pdf_rows: acquire_events and add_rows_to_pdf per group).  A call with
+        the configuration of the one before adds to its histogram; a changed
+        configuration starts a new one."""
+        daq = self._pdf_daq(1)
+        config = (int(tbins), tuple(float(x) for x in trange), int(qbins), tuple(float(x) for x in qrange))
+        pdf = self.gpu_pdf
+        if self.pdf_config != config:
+            self.pdf_config = config
+            pdf.setup_pdf(self.gpu_geometry.nchannels, tbins, trange, qbins, qrange)
+        for gp, n in self._pdf_copies(iterable, nreps, max_steps):
+            self._acquire_copy_rows(daq, gp, n, nreps, pdf.add_hits_to_pdf, pdf.add_rows_to_pdf)
+        return pdf.get_pdfs()
+
+    def _kernel_acquisitions(self, iterable, nreps, ndaq, accumulate):
+        """Per source and propagated copy, ndaq acquisitions of one DAQ copy each
+        through self.gpu_daq, each handed to `accumulate`.  Not batched: the
+        kernel estimator's float sums depend on the order of the acquisitions."""
+        daq = self._pdf_daq(1)
+        for gp, n in self._pdf_copies(iterable, nreps, 100):
+            for c in range(nreps):
+                for _ in range(int(ndaq)):
+                    accumulate(self._acquire_copy(daq, gp, c, n))
+
+    def setup_kernel(self, event_channels, bandwidth_iterable, trange, qrange, nreps=1, ndaq=1, time_only=True,
+                     scale_factor=1.0):
+        """Choose the kernel estimator's per-channel bandwidths from the moments of
+        the sources of bandwidth_iterable (GPUKernelPDF.setup_moments /
+        accumulate_moments / compute_bandwidth) and set the observed event
+        (GPUKernelPDF.setup_kernel) for eval_kernel."""
+        kpdf = self.gpu_pdf_kernel
+        kpdf.setup_moments(self.gpu_geometry.nchannels, trange, qrange, time_only=time_only)
+        self._kernel_acquisitions(bandwidth_iterable, nreps, ndaq, kpdf.accumulate_moments)
+        kpdf.compute_bandwidth(event_channels.hit, event_channels.t, event_channels.q, scale_factor=scale_factor)
+        kpdf.setup_kernel(event_channels.hit, event_channels.t, event_channels.q)
+
+    def eval_kernel(self, event_channels, kernel_iterable, trange, qrange, nreps=1, ndaq=1, time_only=True):
+        """The kernel estimate of the PDF at the event given to setup_kernel, from
+        the sources of kernel_iterable: (hitcount, pdf_value, pdf_uncert)
+        (GPUKernelPDF.get_kernel_eval).  trange, qrange and time_only are
+        setup_kernel's (the estimator keeps them)."""
+        kpdf = self.gpu_pdf_kernel
+        kpdf.clear_kernel()
+        self._kernel_acquisitions(kernel_iterable, nreps, ndaq, kpdf.accumulate_kernel)
+        return kpdf.get_kernel_eval()
+
     def __del__(self):
         ctx = getattr(self, 'context', None)
         if ctx is not None:
@@ -470,6 +644,19 @@ class ShardedSimulation(Simulation):
     def hit_map(self, *args, **kwargs):
         # the map of a rank's photons would have to be reduced over the ranks (SUM; MIN for tmin)
         raise NotImplementedError('hit_map is not sharded: use Simulation')
+
+    # the accumulators of a rank's photons would have to be reduced over the ranks before they are read
+    def eval_pdf(self, *args, **kwargs):
+        raise NotImplementedError('eval_pdf is not sharded: use Simulation')
+
+    def create_pdf(self, *args, **kwargs):
+        raise NotImplementedError('create_pdf is not sharded: use Simulation')
+
+    def setup_kernel(self, *args, **kwargs):
+        raise NotImplementedError('setup_kernel is not sharded: use Simulation')
+
+    def eval_kernel(self, *args, **kwargs):
+        raise NotImplementedError('eval_kernel is not sharded: use Simulation')
 
     def _upload(self, batch_events):
         from chroma.gpu import shard

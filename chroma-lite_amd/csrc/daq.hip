@@ -284,6 +284,93 @@ __global__ void run_daq_many_kernel(uint32_t *rng_states, uint32_t nslots, uint3
     }
 }
 
+// ---- ndaq > 1 for every event of a batch in one launch (chr_daq_acquire_events_many)
+
+// The draws of run_daq_many_kernel for events e = 0 .. nevents-1 over photons
+// [bounds[e], bounds[e+1]), into row e (ndaq copies of nchannels words) of the
+// accumulators.  Only the slots that can draw are launched: slot (b, tid) = tid +
+// ntpb*b with tid < tids = min(ntpb, ndaq) and b < nb = min(max_blocks, max n_e).
+// `width` consecutive work-items share one b: tids rounded up to a power of two below
+// a wave (several b per wave when ndaq < 64) or to whole waves above it, so a photon's
+// candidate word, time, weight and history are uniform over the lanes that share a b.
+// Slot (b, tid) takes part in event e iff b < min(max_blocks, n_e), visits positions
+// b, b + max_blocks, ... there and draws for copies tid, tid + ntpb, ... of a detected
+// photon; its xorwow state and normal-cache pair stay in registers from its first
+// draw to the one store.  The event loop and its skip are wave-uniform (the wave's
+// lowest b in an SGPR, bounds through uniform loads); the candidate word of the
+// slot's first position is read one event ahead, as in run_daq_events_kernel.
+__global__ __launch_bounds__(BLOCK) void run_daq_events_many_kernel(
+    uint32_t *rng_states, uint32_t nslots, uint32_t *normal_cache, const uint32_t *__restrict__ bounds,
+    uint32_t nevents, uint32_t ntpb, uint32_t max_blocks, uint32_t tids, uint32_t width, uint32_t nb, DaqPhotons ph,
+    chr_daq_detector det, const int32_t *__restrict__ cand, uint32_t *time_int, uint32_t *q_int, uint32_t *hist,
+    uint32_t ndaq, float global_weight) {
+    const uint32_t g = blockIdx.x * BLOCK + threadIdx.x;
+    const uint32_t b = g / width, tid = g - b * width;
+    const uint32_t wave_b = __builtin_amdgcn_readfirstlane(b);   // b ascends with g: the wave's lowest
+    const bool mine = tid < tids && b < nb;
+    const uint32_t slot = tid + ntpb * b;
+    const uint32_t first = bounds[0];
+    const uint32_t nch = (uint32_t)det.nchannels;
+    auto head = [&](uint32_t e) -> int {
+        const uint32_t b0 = bounds[e], lim = min(max_blocks, bounds[e + 1] - b0);
+        if (wave_b >= lim) return -1;
+        return mine && b < lim ? cand[b0 - first + b] : -1;
+    };
+    chr_xorwow rng;
+    uint32_t nflag = 0, nextra = 0;
+    bool loaded = false;
+    int next = head(0);
+    for (uint32_t e = 0; e < nevents; ++e) {
+        int channel_index = next;
+        if (e + 1 < nevents) next = head(e + 1);
+        const uint32_t b0 = bounds[e], n = bounds[e + 1] - b0, lim = min(max_blocks, n);
+        if (wave_b >= lim) continue;
+        if (!mine || b >= lim) continue;
+        const size_t row = (size_t)e * ndaq * nch;
+        for (uint32_t pos = b; pos < n; pos += max_blocks) {
+            if (pos != b) channel_index = cand[b0 - first + pos];
+            if (channel_index < 0) continue;
+            const uint32_t photon_id = b0 + pos;
+            const float photon_time = ph.t[photon_id];
+            const float weight = ph.weights[photon_id] * global_weight;
+            const uint32_t history = ph.flags[photon_id];
+            if (!loaded) {
+                load_rng(rng_states, nslots, slot, rng);
+                nflag = normal_cache[slot];
+                nextra = normal_cache[nslots + slot];
+                loaded = true;
+            }
+            for (uint32_t i = tid; i < ndaq; i += ntpb) {
+                if (chr_uniform01(&rng) < weight) {
+                    float time = photon_time + chr_normal(&rng, &nflag, &nextra);
+                    time = time + sample_cdf_xy(rng, det.time_cdf_len, det.d_time_cdf_x, det.d_time_cdf_y);
+                    const float charge =
+                        sample_cdf_xy(rng, det.charge_cdf_len, det.d_charge_cdf_x, det.d_charge_cdf_y);
+                    const uint32_t charge_int = chr_sat_u32(__builtin_roundf(charge / det.charge_unit));
+                    const size_t w = row + (size_t)i * nch + (uint32_t)channel_index;
+                    atomicMin(time_int + w, __float_as_uint(time));
+                    atomicAdd(q_int + w, charge_int);
+                    atomicOr(hist + w, history);
+                }
+            }
+        }
+    }
+    if (loaded) {
+        store_rng(rng_states, nslots, slot, rng);
+        normal_cache[slot] = nflag;
+        normal_cache[nslots + slot] = nextra;
+    }
+}
+
+// what chr_daq_end and begin_acquire's fill leave in the float charges of every row of
+// `row_words` = ndaq*nchannels words: the first nchannels converted, the rest 0
+__global__ __launch_bounds__(BLOCK) void convert_charge_rows_kernel(const uint32_t *q_int, float *q, uint32_t n,
+                                                                    uint32_t row_words, uint32_t nchannels,
+                                                                    float charge_unit) {
+    const uint32_t i = blockIdx.x * BLOCK + threadIdx.x;
+    if (i < n) q[i] = (i % row_words) < nchannels ? (float)q_int[i] * charge_unit : 0.0f;
+}
+
 // daq.cu:147-172
 __global__ __launch_bounds__(BLOCK) void end_kernel(const uint32_t *time_int, float *time, const uint32_t *q_int,
                                                     float *q, uint32_t n, int32_t nchannels, float charge_unit) {
@@ -445,6 +532,86 @@ extern "C" int chr_daq_acquire_events(const chr_photons *ph, int32_t nphotons, c
     }
     hipLaunchKernelGGL(convert_charge_kernel, dim3(grid_for(words)), dim3(BLOCK), 0, stream, d_q_int, d_q,
                        (uint32_t)words, det->charge_unit);
+    CHR_HIP_CHECK(hipGetLastError());
+    // the pinned bounds are rewritten by the next call, and GPUDaq.acquire synchronises too (daq.py:91)
+    CHR_HIP_CHECK(hipStreamSynchronize(stream));
+    return CHR_OK;
+}
+
+extern "C" int chr_daq_acquire_events_many(const chr_photons *ph, int32_t nphotons, const int64_t *h_bounds,
+                                           int32_t nevents, uint32_t *d_rng_states, uint32_t rng_nslots,
+                                           uint32_t *d_normal_cache, uint32_t detection_state,
+                                           const uint32_t *d_solid_map, const chr_daq_detector *det,
+                                           uint32_t *d_time_int, uint32_t *d_q_int, uint32_t *d_history, float *d_q,
+                                           int32_t ndaq, float global_weight, int32_t ntpb, int32_t max_blocks,
+                                           void *vstream) {
+    if (!ph || !ph->d_t || !ph->d_flags || !ph->d_last_hit_triangles || !ph->d_weights || !h_bounds ||
+        !d_rng_states || !d_normal_cache || !d_solid_map || !det || !det->d_solid_id_to_channel_index ||
+        !d_time_int || !d_q_int || !d_history || !d_q)
+        return chr::fail(CHR_ERR_INVALID, "chr_daq_acquire_events_many: null argument");
+    if (!det->d_time_cdf_x || !det->d_time_cdf_y || !det->d_charge_cdf_x || !det->d_charge_cdf_y ||
+        det->time_cdf_len < 2 || det->charge_cdf_len < 2)
+        return chr::fail(CHR_ERR_INVALID, "chr_daq_acquire_events_many: time/charge CDFs missing");
+    if (ndaq < 2)
+        return chr::fail(CHR_ERR_INVALID, "chr_daq_acquire_events_many: ndaq = %d (chr_daq_acquire_events runs ndaq = 1)",
+                         ndaq);
+    if (nevents < 0 || nphotons < 0 || ntpb <= 0 || max_blocks <= 0 || det->nchannels <= 0)
+        return chr::fail(CHR_ERR_INVALID,
+                         "chr_daq_acquire_events_many: bad event count / launch shape / channel count");
+    if (ntpb > 1024) return chr::fail(CHR_ERR_INVALID, "chr_daq_acquire_events_many: nthreads_per_block > 1024");
+    if (h_bounds[0] < 0 || h_bounds[nevents] > nphotons)
+        return chr::fail(CHR_ERR_INVALID, "chr_daq_acquire_events_many: bounds [%lld, %lld] outside the %d photons",
+                         (long long)h_bounds[0], (long long)h_bounds[nevents], nphotons);
+    int64_t max_n = 0;
+    for (int32_t e = 0; e < nevents; ++e) {
+        if (h_bounds[e + 1] < h_bounds[e])
+            return chr::fail(CHR_ERR_INVALID, "chr_daq_acquire_events_many: bounds decrease at event %d", e);
+        max_n = std::max(max_n, h_bounds[e + 1] - h_bounds[e]);
+    }
+    // the slots of the per-event launches: blocks b < min(max_blocks, n_e) of ntpb each
+    const uint32_t nb = (uint32_t)std::min<int64_t>(max_blocks, max_n);
+    if ((uint64_t)ntpb * nb > rng_nslots)
+        return chr::fail(CHR_ERR_INVALID, "chr_daq_acquire_events_many: %llu slots needed, %u rng states",
+                         (unsigned long long)ntpb * nb, rng_nslots);
+    const uint64_t row_words = (uint64_t)ndaq * (uint32_t)det->nchannels;
+    if (nevents > 0 && row_words > 0x80000000u / (uint32_t)nevents)      // the product may not fit 64 bits
+        return chr::fail(CHR_ERR_INVALID,
+                         "chr_daq_acquire_events_many: %d events of %d copies of %d channels exceed 2^31 words",
+                         nevents, ndaq, det->nchannels);
+    const uint64_t words = (uint64_t)nevents * row_words;
+    // only the work-items that can draw: tid < min(ntpb, ndaq); `width` of them share a b
+    const uint32_t tids = (uint32_t)std::min(ntpb, ndaq);
+    uint32_t width = 1;
+    if (tids >= 64) width = (tids + 63u) & ~63u;
+    else while (width < tids) width <<= 1;
+    if ((uint64_t)nb * width > 0xFFFFFF00u)      // width < 2 * ntpb: only with more than 2^31 rng states
+        return chr::fail(CHR_ERR_INVALID, "chr_daq_acquire_events_many: %u blocks of %u work-items exceed one launch",
+                         nb, width);
+    if (nevents == 0) return CHR_OK;
+
+    hipStream_t stream = (hipStream_t)vstream;
+    hipLaunchKernelGGL(begin_kernel, dim3(grid_for(words)), dim3(BLOCK), 0, stream, d_time_int, d_q_int, d_history,
+                       (uint32_t)words, __builtin_bit_cast(uint32_t, 1e9f));
+    CHR_HIP_CHECK(hipGetLastError());
+    if (nb > 0) {
+        const uint32_t first = (uint32_t)h_bounds[0], span = (uint32_t)(h_bounds[nevents] - h_bounds[0]);
+        EventBuffers *buf = nullptr;
+        CHR_TRY(event_buffers((size_t)nevents + 1, span, &buf));
+        for (int32_t e = 0; e <= nevents; ++e) buf->h_bounds[e] = (uint32_t)h_bounds[e];
+        CHR_HIP_CHECK(hipMemcpyAsync(buf->d_bounds, buf->h_bounds, ((size_t)nevents + 1) * 4, hipMemcpyHostToDevice,
+                                     stream));
+        DaqPhotons p{ph->d_t, ph->d_weights, ph->d_flags, ph->d_last_hit_triangles};
+        hipLaunchKernelGGL(candidates_kernel, dim3(grid_for(span)), dim3(BLOCK), 0, stream, p, first, span,
+                           d_solid_map, *det, detection_state, buf->d_cand);
+        CHR_HIP_CHECK(hipGetLastError());
+        hipLaunchKernelGGL(run_daq_events_many_kernel, dim3(grid_for((uint64_t)nb * width)), dim3(BLOCK), 0, stream,
+                           d_rng_states, rng_nslots, d_normal_cache, buf->d_bounds, (uint32_t)nevents, (uint32_t)ntpb,
+                           (uint32_t)max_blocks, tids, width, nb, p, *det, buf->d_cand, d_time_int, d_q_int,
+                           d_history, (uint32_t)ndaq, global_weight);
+        CHR_HIP_CHECK(hipGetLastError());
+    }
+    hipLaunchKernelGGL(convert_charge_rows_kernel, dim3(grid_for(words)), dim3(BLOCK), 0, stream, d_q_int, d_q,
+                       (uint32_t)words, (uint32_t)row_words, (uint32_t)det->nchannels, det->charge_unit);
     CHR_HIP_CHECK(hipGetLastError());
     // the pinned bounds are rewritten by the next call, and GPUDaq.acquire synchronises too (daq.py:91)
     CHR_HIP_CHECK(hipStreamSynchronize(stream));

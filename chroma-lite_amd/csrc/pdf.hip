@@ -58,6 +58,31 @@ __global__ __launch_bounds__(BLOCK) void bin_hits_kernel(int nchannels, const fl
     }
 }
 
+// bin_hits_kernel for nrows consecutive rows of nchannels words (row r of channel c at
+// r*nchannels + c): one work-item per channel walks the rows in order, so the
+// histogram equals nrows launches of bin_hits_kernel
+__global__ __launch_bounds__(BLOCK) void bin_hits_rows_kernel(int nchannels, int nrows, const float *channel_q,
+                                                              const float *channel_time, uint32_t *hitcount,
+                                                              int tbins, float tmin, float tmax, int qbins,
+                                                              float qmin, float qmax, uint32_t *pdf) {
+    const int id = blockIdx.x * BLOCK + threadIdx.x;
+    if (id >= nchannels) return;
+    uint32_t hits = 0;
+    uint32_t *mine = pdf + (size_t)id * tbins * qbins;
+    for (int r = 0; r < nrows; r++) {
+        const size_t w = (size_t)r * nchannels + id;
+        const float q = (float)sat_u32(channel_q[w]);
+        const float t = channel_time[w];
+        if (t < 1e8f && t >= tmin && t < tmax && q >= qmin && q < qmax) {
+            hits += 1u;
+            const int tbin = min((int)((t - tmin) / (tmax - tmin) * (float)tbins), tbins - 1);
+            const int qbin = min((int)((q - qmin) / (qmax - qmin) * (float)qbins), qbins - 1);
+            mine[(size_t)tbin * qbins + qbin] += 1u;
+        }
+    }
+    hitcount[id] += hits;
+}
+
 // pdf.cu:34-96: per channel, over the ndaq DAQ copies in order
 __global__ __launch_bounds__(BLOCK) void bincount_kernel(int nchannels, int ndaq, const uint32_t *event_hit,
                                                          const float *event_time, const float *mc_time,
@@ -214,6 +239,23 @@ extern "C" int chr_pdf_bin_hits(int32_t nchannels, const float *d_channel_q, con
     if (nchannels <= 0) return CHR_OK;
     hipLaunchKernelGGL(bin_hits_kernel, dim3(grid_for(nchannels)), dim3(BLOCK), 0, (hipStream_t)stream, nchannels,
                        d_channel_q, d_channel_time, d_hitcount, tbins, tmin, tmax, qbins, qmin, qmax, d_pdf);
+    CHR_HIP_CHECK(hipGetLastError());
+    return CHR_OK;
+}
+
+extern "C" int chr_pdf_bin_hits_rows(int32_t nchannels, int32_t nrows, const float *d_channel_q,
+                                     const float *d_channel_time, uint32_t *d_hitcount, int32_t tbins, float tmin,
+                                     float tmax, int32_t qbins, float qmin, float qmax, uint32_t *d_pdf,
+                                     void *stream) {
+    if (!d_channel_q || !d_channel_time || !d_hitcount || !d_pdf)
+        return chr::fail(CHR_ERR_INVALID, "chr_pdf_bin_hits_rows: null argument");
+    if (tbins <= 0 || qbins <= 0 || !(tmax > tmin) || !(qmax > qmin))
+        return chr::fail(CHR_ERR_INVALID, "chr_pdf_bin_hits_rows: empty binning");
+    if (nrows < 0) return chr::fail(CHR_ERR_INVALID, "chr_pdf_bin_hits_rows: nrows < 0");
+    if (nchannels <= 0 || nrows == 0) return CHR_OK;
+    hipLaunchKernelGGL(bin_hits_rows_kernel, dim3(grid_for(nchannels)), dim3(BLOCK), 0, (hipStream_t)stream,
+                       nchannels, nrows, d_channel_q, d_channel_time, d_hitcount, tbins, tmin, tmax, qbins, qmin,
+                       qmax, d_pdf);
     CHR_HIP_CHECK(hipGetLastError());
     return CHR_OK;
 }

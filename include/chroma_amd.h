@@ -571,6 +571,33 @@ int chr_daq_acquire_events(const chr_photons *ph, int32_t nphotons, const int64_
                            uint32_t *d_time_int, uint32_t *d_q_int, uint32_t *d_history, float *d_q,
                            float global_weight, int32_t nthreads_per_block, int32_t max_blocks, void *stream);
 
+/* chr_daq_acquire_events for ndaq > 1 (run_daq_many, daq.cu:85-145): the DAQ of
+ * ndaq copies for the nevents consecutive photon ranges of h_bounds, in a
+ * number of launches that does not depend on nevents.  Outputs are nevents rows
+ * of ndaq*nchannels words, row e = event e, copy i of channel c at i*nchannels
+ * + c inside it: d_time_int (whose bit view as f32 is what chr_daq_end writes),
+ * d_q_int, d_history, and d_q as chr_daq_end after GPUDaq.begin_acquire's fill
+ * leaves it (the first nchannels words of a row converted, the rest 0).  Rows,
+ * the RNG slot states and d_normal_cache afterwards are bit-identical to
+ * chr_daq_begin(1e9) + chr_daq_acquire(start = h_bounds[e], n = h_bounds[e+1] -
+ * h_bounds[e], ndaq, stride = nchannels) + chr_daq_end for e = 0, 1, ...: slot
+ * tid + nthreads_per_block*b draws in event e iff b < min(max_blocks, n_e), for
+ * positions b, b+max_blocks, ... of it and copies tid, tid+nthreads_per_block,
+ * ... < ndaq of each detected photon (uniform, normal, time CDF, charge CDF),
+ * events ascending.  A channel index at or beyond nchannels counts as not
+ * detected (chr_daq_acquire would write it through, into a later copy or row).
+ * CHR_ERR_INVALID before any launch for null arguments, missing CDFs, ndaq <
+ * 2, nthreads_per_block > 1024, nevents < 0, h_bounds decreasing / below 0 /
+ * beyond nphotons, nthreads_per_block*min(max_blocks, max n_e) > rng_nslots, or
+ * nevents*ndaq*nchannels > 2^31; nevents == 0 is CHR_OK and touches nothing.
+ * Synchronous. */
+int chr_daq_acquire_events_many(const chr_photons *ph, int32_t nphotons, const int64_t *h_bounds, int32_t nevents,
+                                uint32_t *d_rng_states, uint32_t rng_nslots, uint32_t *d_normal_cache,
+                                uint32_t detection_state, const uint32_t *d_solid_map, const chr_daq_detector *det,
+                                uint32_t *d_time_int, uint32_t *d_q_int, uint32_t *d_history, float *d_q,
+                                int32_t ndaq, float global_weight, int32_t nthreads_per_block, int32_t max_blocks,
+                                void *stream);
+
 /* Detected photons per channel, ACCUMULATED into d_counts[nchannels] (u32; the
  * caller zeroes it): the selection of count_photon_hits (propagate.cu:172-199)
  * histogrammed by channel.  No reference counterpart -- it is the per-rank
@@ -678,6 +705,13 @@ int chr_hitmap_accumulate_host(const chr_photons *ph, int32_t start_photon, int3
 int chr_pdf_bin_hits(int32_t nchannels, const float *d_channel_q, const float *d_channel_time,
                      uint32_t *d_hitcount, int32_t tbins, float tmin, float tmax, int32_t qbins, float qmin,
                      float qmax, uint32_t *d_pdf, void *stream);
+/* chr_pdf_bin_hits for nrows consecutive rows of nchannels words (row r of
+ * channel c at r*nchannels + c in d_channel_q / d_channel_time): one work-item
+ * per channel walks the rows in order; d_hitcount and d_pdf afterwards equal
+ * nrows calls of chr_pdf_bin_hits, one per row.  No reference counterpart. */
+int chr_pdf_bin_hits_rows(int32_t nchannels, int32_t nrows, const float *d_channel_q, const float *d_channel_time,
+                          uint32_t *d_hitcount, int32_t tbins, float tmin, float tmax, int32_t qbins, float qmin,
+                          float qmax, uint32_t *d_pdf, void *stream);
 /* replaces: accumulate_bincount (pdf.cu:34-96; GPUPDF.accumulate_pdf_eval,
  * pdf.py:296-316).  d_work_queues: nhit*(ndaq+1) u32, word 0 of each queue
  * = 1 + queued entries (the caller fills 1). */
