@@ -8,6 +8,7 @@ from chroma.gpu.detector import GPUDetector  # noqa: F401
 from chroma.gpu.photon import GPUPhotons, GPUPhotonsSlice, propagate_batches, generate_photons  # noqa: F401
 from chroma.gpu.tracks import PhotonTracks  # noqa: F401
 from chroma.gpu.hitmap import GPUHitMap, HostHitMap, HitMap  # noqa: F401
+from chroma.gpu.library import GPUPhotonLibrary, HostPhotonLibrary  # noqa: F401
 from chroma.gpu.daq import GPUDaq, GPUChannels, GPUEventChannels  # noqa: F401
 from chroma.gpu.pdf import GPUPDF, GPUKernelPDF  # noqa: F401
 from chroma.gpu.render import GPURays  # noqa: F401

@@ -77,6 +77,11 @@ class HitMapDesc(ctypes.Structure):
                 ('d_skipped', c_vp)]
 
 
+class LibraryEntriesDesc(ctypes.Structure):
+    """chr_library_entries: the CSR table of the events' entries."""
+    _fields_ = [('nevents', c_u32), ('offsets', c_vp), ('source', c_vp), ('nphotons', c_vp), ('t', c_vp)]
+
+
 class PropagateStats(ctypes.Structure):
     _fields_ = [('steps_run', c_u32), ('launches', c_u32), ('final_alive', c_u32), ('stack_overflows', c_u32),
                 ('kernel_ms', ctypes.c_double), ('nodes_visited', c_u64), ('triangles_tested', c_u64),
@@ -174,6 +179,15 @@ _SIGNATURES = {
     'chr_hitmap_last_path': (c_i32, []),
     'chr_hitmap_accumulate_host': (c_i32, [ctypes.POINTER(PhotonsDesc), c_i32, c_i32, c_u32, c_vp, c_vp,
                                            ctypes.POINTER(HitMapDesc)]),
+    'chr_library_expect': (c_i32, [ctypes.POINTER(HitMapDesc), ctypes.POINTER(LibraryEntriesDesc), c_vp, c_vp, c_vp,
+                                   c_vp]),
+    'chr_library_last_path': (c_i32, []),
+    'chr_library_sample': (c_i32, [ctypes.POINTER(HitMapDesc), ctypes.POINTER(LibraryEntriesDesc), c_vp, c_u32, c_vp,
+                                   c_vp, c_vp, c_vp]),
+    'chr_library_expect_host': (c_i32, [ctypes.POINTER(HitMapDesc), ctypes.POINTER(LibraryEntriesDesc), c_vp, c_vp,
+                                        c_vp]),
+    'chr_library_sample_host': (c_i32, [ctypes.POINTER(HitMapDesc), ctypes.POINTER(LibraryEntriesDesc), c_vp, c_u32,
+                                        c_vp, c_vp, c_vp]),
     'chr_pdf_bin_hits': (c_i32, [c_i32, c_vp, c_vp, c_vp, c_i32, c_f32, c_f32, c_i32, c_f32, c_f32, c_vp, c_vp]),
     'chr_pdf_bin_hits_rows': (c_i32, [c_i32, c_i32, c_vp, c_vp, c_vp, c_i32, c_f32, c_f32, c_i32, c_f32, c_f32, c_vp,
                                       c_vp]),

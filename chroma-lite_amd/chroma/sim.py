@@ -408,6 +408,12 @@ class Simulation(object):
                                            max_blocks, max_steps, use_weights)
               GPUHitMap.accumulate(m) for m in made                 # draws nothing
         """
+        return self._hit_map_device(gensteps, nsources, tbins, trange, earliest, weights, max_steps,
+                                    photons_per_batch, use_weights).get()
+
+    def _hit_map_device(self, gensteps, nsources, tbins, trange, earliest, weights, max_steps, photons_per_batch,
+                        use_weights):
+        """hit_map's work; the GPUHitMap itself, nothing downloaded but `last_exhausted`."""
         if not hasattr(self.detector, 'num_channels') or self.gpu_geometry.nchannels <= 0:
             raise ValueError('hit_map needs a detector with channels')
         from chroma import gensteps as gs
@@ -433,7 +439,54 @@ class Simulation(object):
             for m in made:
                 hm.accumulate(m)
         self.last_pipeline = (len(batches), calls)
-        return hm.get()
+        return hm
+
+    # ------------------------------------------------------------ photon library
+    def build_library(self, grid, material, photons_per_voxel, tbins=0, trange=None, earliest=True,
+                      wavelength_range=(380.0, 500.0), max_steps=1000, photons_per_batch=1000000, use_weights=False):
+        """A chroma.gpu.GPUPhotonLibrary of `grid` (chroma.library.VoxelGrid): the
+        hit map of grid.flashes(material, photons_per_voxel, wavelength_range) --
+        one isotropic flash at every voxel centre, source id = voxel id --, kept
+        on the device (nothing of it is downloaded) and carrying the grid.  The
+        call sequence, on which the RNG stream depends, is hit_map's for those
+        flashes."""
+        hm = self._hit_map_device(grid.flashes(material, photons_per_voxel, wavelength_range), grid.nvoxels, tbins,
+                                  trange, earliest, False, max_steps, photons_per_batch, use_weights)
+        return gpu.GPUPhotonLibrary(hm, grid=grid)
+
+    def simulate_library(self, library, iterable, sample=True):
+        """One event.Event per Gensteps of `iterable` with `channels` filled from a
+        GPUPhotonLibrary instead of a propagation: sampled (hit = n > 0, q = n, t
+        drawn from the library's time histogram or its earliest time), or with
+        sample=False the expected values (q = mu, hit = mu > 0, t = tfirst).  The
+        library needs its grid.  ev.nphotons is the photons the steps name; no
+        photon is made.
+
+        The call sequence, on which the RNG stream depends:
+          parts = list(iterable);
+          groups = consecutive runs of max(1, daq_group_bytes // (8 * nchannels)) parts;
+          for each group, just before its first event is yielded:
+              entries = chroma.library.entries_from_gensteps(library.grid, group)
+              sample:     library.sample(entries, rng_states).get()   # chr_library_sample, all slots
+              otherwise:  chroma.gpu.library.expected_channels(library.expect(entries).get())   # draws nothing
+        """
+        from chroma.gpu.library import expected_channels
+        from chroma.library import entries_from_gensteps
+        if library.grid is None:
+            raise ValueError('simulate_library needs a library that carries its grid')
+        parts = [iterable] if isinstance(iterable, Gensteps) else list(iterable)
+        per_group = max(1, int(self.daq_group_bytes) // (8 * int(library.nchannels)))
+        for first in range(0, len(parts), per_group):
+            group = parts[first:first + per_group]
+            entries = entries_from_gensteps(library.grid, group)
+            if sample:
+                channels = library.sample(entries, self.rng_states).get()
+            else:
+                channels = expected_channels(library.expect(entries).get())
+            for g, ch in zip(group, channels):
+                ev = event.Event(channels=ch)
+                ev.nphotons = g.nphotons
+                yield ev
 
     # ------------------------------------------------------------ likelihood support
     def _pdf_sources(self, iterable):
@@ -644,6 +697,13 @@ class ShardedSimulation(Simulation):
     def hit_map(self, *args, **kwargs):
         # the map of a rank's photons would have to be reduced over the ranks (SUM; MIN for tmin)
         raise NotImplementedError('hit_map is not sharded: use Simulation')
+
+    def build_library(self, *args, **kwargs):
+        raise NotImplementedError('build_library is not sharded: use Simulation')
+
+    def simulate_library(self, *args, **kwargs):
+        # every rank would draw the same channels from a different stream
+        raise NotImplementedError('simulate_library is not sharded: use Simulation')
 
     # the accumulators of a rank's photons would have to be reduced over the ranks before they are read
     def eval_pdf(self, *args, **kwargs):

@@ -693,6 +693,105 @@ int chr_hitmap_accumulate_host(const chr_photons *ph, int32_t start_photon, int3
                                uint32_t detection_state, const uint32_t *h_solid_map,
                                const int32_t *h_solid_id_to_channel_index, const chr_hitmap_desc *desc);
 
+/* --------------------------------------------------------- photon library
+ * The consumer of a hit map: from the map of a set of sources (the library,
+ * a chr_hitmap_desc used READ-ONLY: emitted, counts, optional tmin, optional
+ * thist with t_lo and inv; wsum and d_skipped are ignored) and the entries of
+ * some events, every event's per-channel expected charge and earliest time
+ * (chr_library_expect), or a sampled charge and time per channel
+ * (chr_library_sample), without propagating a photon.  No reference
+ * counterpart.
+ *
+ * The entries are a CSR table: event e owns entries offsets[e] ..
+ * offsets[e+1]-1 (offsets ascending), entry i says "nphotons[i] photons were
+ * made at time t[i] where source source[i] was flashed".  An event's entries
+ * are used in the order given.
+ *
+ * Expected values, for event e and channel c (csrc/library.h, one text for
+ * the device, the host twin and, restated, tests/library_model.py):
+ *   1. mu = 0.0f, tfirst = +inf.
+ *   2. for the entries i of e in order, s = source[i]:
+ *   3.   s >= nsources: the entry adds nothing and is counted once (per entry,
+ *        not per channel) in *skipped; emitted[s] == 0: it adds nothing.
+ *   4.   w = (float)nphotons[i] / (float)emitted[s], one IEEE divide of two
+ *        round-to-nearest conversions; k = counts[s*nchannels + c];
+ *        mu = fmaf(w, (float)k, mu).
+ *   5.   tmin kept, k > 0 and key = tmin[s*nchannels + c] != 0xFFFFFFFF:
+ *        cand = t[i] + time_of_key(key) (the hit map's key undone: key ^
+ *        0x80000000 when its top bit is set, else key ^ 0xFFFFFFFF, as float
+ *        bits); tfirst = cand when cand < tfirst, so a NaN is never taken.
+ * mu[e*nchannels + c] and, only when the library keeps tmin,
+ * tfirst[e*nchannels + c] are written; every word has one writer, there is no
+ * RNG and no atomic but *skipped, so the outputs are a function of the inputs
+ * alone, bit for bit.
+ *
+ * Sampled channels.  Pairs are numbered k = e*nchannels + c, npairs =
+ * nevents*nchannels.  T = min(nslots, npairs) work-items run; work-item j loads
+ * rng slot j once, handles pairs j, j+T, j+2T, ... in ascending order and
+ * stores the state back; slots >= T are untouched.  For a pair: n = 0, mu and
+ * tfirst as above, tdrawn = +inf, an empty chr_normal cache (local to the pair,
+ * dropped after it); then for the entries in order, those of step 3 skipped:
+ *   1. m = w * (float)k, one multiply.
+ *   2. n_i = poisson(m): m NaN or <= 0: 0, nothing drawn.  m < 32: Knuth's
+ *      product, p = 1, count factors p *= chr_uniform01() until p <=
+ *      chr_expf(-m) (at most 1024 factors), n_i = factors - 1.  Otherwise
+ *      n_i = chr_sat_u32(fmaf(sqrtf(m), z, m) + 0.5f), z = chr_normal(): a
+ *      normal approximation rounded to the nearest integer, negatives to 0,
+ *      2^32 and above to 2^32-1.  n = min(n + n_i, 2^32-1).
+ *   3. thist kept and n_i > 0: total = the sum of the ntbins words of (s, c)
+ *      (uint32); total > 0: for each of the first min(n_i,
+ *      CHR_LIBRARY_MAX_TIME_DRAWS) photons: u = chr_uniform01(), r =
+ *      min(chr_sat_u32(u * (float)total), total-1), b = the first bin whose
+ *      running integer sum exceeds r, x = (float)b + chr_uniform01(), cand =
+ *      t[i] + fmaf(x, width, t_lo) with width = 1.0f / inv; tdrawn = cand when
+ *      cand < tdrawn.  The cap is an approximation: an entry that gives a
+ *      channel more than 64 photons takes the earliest of 64 drawn times, not
+ *      of n_i, so the earliest time of a bright channel is biased late by at
+ *      most the spread of the 64-sample minimum.
+ * n_out[k] = n; t_out[k] = 1e9f (the DAQ's time of a channel without a hit)
+ * when n == 0, else tdrawn when thist is kept, else tfirst (+inf when the
+ * library holds no time for the pair). */
+typedef struct chr_library_entries {
+    uint32_t nevents;
+    const uint32_t *offsets;          /* nevents + 1 */
+    const uint32_t *source, *nphotons;/* per entry */
+    const float *t;                   /* per entry */
+} chr_library_entries;
+#define CHR_LIBRARY_MAX_TIME_DRAWS 64u
+
+/* Expected values by the rule above; *d_skipped (u64) is ADDED to.  d_tfirst
+ * may be NULL when the library keeps no tmin.  Two paths with identical words:
+ * wide (4 channels per lane through 16-byte loads; nchannels a multiple of 4
+ * and counts, tmin, mu, tfirst 16-byte aligned) and narrow (1 channel per
+ * lane); the environment's CHR_LIBRARY_PATH=n forces the narrow one.
+ * CHR_ERR_INVALID before anything is read through a pointer for: a null
+ * required pointer (desc, entries, d_emitted, d_counts, d_mu, d_skipped,
+ * d_tfirst while tmin is kept; offsets, source, nphotons, t while nevents >
+ * 0); d_thist null while ntbins > 0 or non-null while ntbins == 0; nsources ==
+ * 0 or nchannels <= 0; an array over 2^31 words (the map's, or nevents *
+ * nchannels); inv not finite or not positive while ntbins > 0.  The device
+ * entries do not read offsets on the host: the caller passes them ascending
+ * (chroma.library.LibraryEntries checks; the host twins check and refuse).
+ * nevents == 0 is CHR_OK and touches nothing.  Async on `stream`. */
+int chr_library_expect(const chr_hitmap_desc *lib, const chr_library_entries *entries, float *d_mu, float *d_tfirst,
+                       uint64_t *d_skipped, void *stream);
+/* The path of the calling thread's last chr_library_expect that launched:
+ * 0 narrow, 1 wide, -1 none yet. */
+int chr_library_last_path(void);
+/* Sampled channels by the rule above: d_n[npairs] u32, d_t[npairs] f32,
+ * d_rng_states as chr_init_rng makes them (6 * nslots words), *d_skipped added
+ * to.  The refusals of chr_library_expect, d_n / d_t / d_rng_states required,
+ * and nslots == 0 or 6 * nslots > 2^31.  Async on `stream`. */
+int chr_library_sample(const chr_hitmap_desc *lib, const chr_library_entries *entries, uint32_t *d_rng_states,
+                       uint32_t nslots, uint32_t *d_n, float *d_t, uint64_t *d_skipped, void *stream);
+/* The same on the host (no GPU needed): every pointer addresses HOST memory.
+ * Word-identical to the device entries (one source, csrc/library.h), with the
+ * same refusals and one more: offsets not ascending. */
+int chr_library_expect_host(const chr_hitmap_desc *lib, const chr_library_entries *entries, float *h_mu,
+                            float *h_tfirst, uint64_t *h_skipped);
+int chr_library_sample_host(const chr_hitmap_desc *lib, const chr_library_entries *entries, uint32_t *h_rng_states,
+                            uint32_t nslots, uint32_t *h_n, float *h_t, uint64_t *h_skipped);
+
 /* ------------------------------------------------------------------- PDF
  * replaces: chroma/cuda/pdf.cu, launched by GPUPDF / GPUKernelPDF
  * (chroma/gpu/pdf.py:7-372).  Inputs are GPUChannels words (t, q: f32; DAQ
