@@ -82,6 +82,11 @@ class LibraryEntriesDesc(ctypes.Structure):
     _fields_ = [('nevents', c_u32), ('offsets', c_vp), ('source', c_vp), ('nphotons', c_vp), ('t', c_vp)]
 
 
+class LibraryObservedDesc(ctypes.Structure):
+    """chr_library_observed: the observed event a log-likelihood scores hypotheses against."""
+    _fields_ = [('nobs', c_vp), ('tobs', c_vp), ('mode', c_u32), ('floor', c_f32), ('tfloor', c_f32)]
+
+
 class PropagateStats(ctypes.Structure):
     _fields_ = [('steps_run', c_u32), ('launches', c_u32), ('final_alive', c_u32), ('stack_overflows', c_u32),
                 ('kernel_ms', ctypes.c_double), ('nodes_visited', c_u64), ('triangles_tested', c_u64),
@@ -188,6 +193,11 @@ _SIGNATURES = {
                                         c_vp]),
     'chr_library_sample_host': (c_i32, [ctypes.POINTER(HitMapDesc), ctypes.POINTER(LibraryEntriesDesc), c_vp, c_u32,
                                         c_vp, c_vp, c_vp]),
+    'chr_library_loglike': (c_i32, [ctypes.POINTER(HitMapDesc), ctypes.POINTER(LibraryEntriesDesc),
+                                    ctypes.POINTER(LibraryObservedDesc), c_vp, c_vp, c_vp, c_vp]),
+    'chr_library_loglike_last_path': (c_i32, []),
+    'chr_library_loglike_host': (c_i32, [ctypes.POINTER(HitMapDesc), ctypes.POINTER(LibraryEntriesDesc),
+                                         ctypes.POINTER(LibraryObservedDesc), c_vp, c_vp, c_vp]),
     'chr_pdf_bin_hits': (c_i32, [c_i32, c_vp, c_vp, c_vp, c_i32, c_f32, c_f32, c_i32, c_f32, c_f32, c_vp, c_vp]),
     'chr_pdf_bin_hits_rows': (c_i32, [c_i32, c_i32, c_vp, c_vp, c_vp, c_i32, c_f32, c_f32, c_i32, c_f32, c_f32, c_vp,
                                       c_vp]),

@@ -1,7 +1,10 @@
 """Photon-library lookup: from a hit map (the library) and the entries of some
 events, every event's expected charge and earliest time per channel, or sampled
 channels, on the device without propagating a photon (chr_library_expect,
-chr_library_sample; include/chroma_amd.h documents both rules).
+chr_library_sample; include/chroma_amd.h documents both rules) -- and the way
+back: the log-likelihood of one observed event under many hypotheses, each a set
+of entries (chr_library_loglike; chroma.likelihood.LibraryLikelihood scans and
+fits with it).
 
 GPUPhotonLibrary holds the map's arrays on the device; HostPhotonLibrary is the
 same over host arrays through the host twins (the kernels' source built by the
@@ -11,6 +14,7 @@ host compiler, word-identical, no GPU needed).
     entries = entries_from_gensteps(grid, [steps])
     table = lib.expect(entries).get()                  # .mu, .tfirst: (nevents, nchannels)
     channels = lib.sample(entries, rng_states).get()   # one event.Channels per event
+    ll = lib.log_likelihood(entries, n, t).get().ll    # per hypothesis (event of the table), float64
 """
 import ctypes
 
@@ -56,6 +60,26 @@ class Sampled(object):
         return [event.Channels(n[e] > 0, t[e].copy(), n[e].astype(np.float32)) for e in range(self.nevents)]
 
 
+class LogLikelihood(object):
+    """log_likelihood()'s outputs where they were computed: `words` (int64, one per
+    hypothesis, in units of 2^-20), `bad` (uint32: the channels whose term was a NaN
+    and counted as 0), `skipped`; get() brings them to the host and adds `ll`, the
+    log-likelihoods as float64 (words / 2**20), with skipped as an int."""
+
+    def __init__(self, nhypotheses, words, bad, skipped, host):
+        self.nhypotheses, self.words, self.bad, self.skipped, self._host = nhypotheses, words, bad, skipped, host
+        self.ll = None
+
+    def get(self):
+        out = LogLikelihood(self.nhypotheses, self._host(self.words), self._host(self.bad),
+                            int(self._host(self.skipped)[0]), lambda a: a)
+        out.ll = out.words.astype(np.float64) / 2.0 ** 20
+        return out
+
+
+MODES = {'poisson': 0, 'hit': 1}
+
+
 def expected_channels(expected):
     """One event.Channels per event of a host Expected: q = mu, hit = mu > 0, t =
     tfirst where hit (1e9 elsewhere, and everywhere when the library keeps no tmin)."""
@@ -71,6 +95,7 @@ def expected_channels(expected):
 
 class _Library(object):
     """The scalars and the four arrays of a library; subclasses say where they live."""
+    last_loglike_path = None
 
     def _setup(self, source, grid):
         if grid is not None and not isinstance(grid, VoxelGrid):
@@ -110,6 +135,37 @@ class _Library(object):
         if entries.nevents * self.nchannels > MAX_WORDS:
             raise ValueError('%d events x %d channels exceed 2^31 words' % (entries.nevents, self.nchannels))
         return entries
+
+    def default_tfloor(self, floor):
+        """floor / (t_hi - t_lo) of the library's time histogram as float32: the noise time
+        density that normalises the time term of log_likelihood."""
+        if self.tbins <= 0:
+            raise ValueError('the library keeps no time histogram')
+        return np.float32(float(np.float32(floor)) * float(self.inv) / self.tbins)
+
+    def _observed(self, n, t, mode, floor, tfloor):
+        """The chr_library_observed of an observed event and the arrays it points into."""
+        if mode not in MODES:
+            raise ValueError("mode must be 'poisson' or 'hit'")
+        if t is not None and self.thist is None:
+            raise ValueError('observed times need a library with a time histogram')
+        if tfloor is None:
+            tfloor = 0.0 if t is None else self.default_tfloor(floor)
+        floor, tfloor = np.float32(floor), np.float32(tfloor)
+        if not (floor >= 0 and tfloor >= 0):
+            raise ValueError('floor = %r and tfloor = %r must not be negative or NaN' % (floor, tfloor))
+        n = self._observed_array(n, np.uint32, 'n')
+        t = None if t is None else self._observed_array(t, np.float32, 't')
+        return (n, t), _native.LibraryObservedDesc(self._ptr(n), self._ptr(t), MODES[mode], float(floor), float(tfloor))
+
+    def _host_observed_array(self, a, dtype, name):
+        a = np.asarray(a)
+        out = np.ascontiguousarray(a, dtype=dtype).reshape(-1)
+        if out.size != self.nchannels:
+            raise ValueError('%s holds %d words for %d channels' % (name, out.size, self.nchannels))
+        if dtype == np.uint32 and not np.array_equal(out.astype(np.float64), a.reshape(-1)):
+            raise ValueError('%s does not fit uint32' % name)
+        return out
 
     def words(self):
         """The library's arrays on the host, as the device holds them (None where not kept)."""
@@ -200,6 +256,42 @@ class GPUPhotonLibrary(_Library):
         out._keep = keep               # the entries' device arrays, until the launch has run
         return out
 
+    def _observed_array(self, a, dtype, name):
+        from chroma.gpu import gpuarray as ga
+        if isinstance(a, ga.GPUArray):                 # e.g. a Sampled's n and t: used where they are
+            if a.dtype != dtype or a.size != self.nchannels:
+                raise ValueError('%s: a device array of %d %s words for %d channels' % (name, a.size, a.dtype,
+                                                                                        self.nchannels))
+            return a
+        return ga.to_gpu(self._host_observed_array(a, dtype, name))
+
+    def log_likelihood(self, entries, n, t=None, mode='poisson', floor=1e-3, tfloor=None):
+        """The log-likelihood of one observed event under every hypothesis of `entries`
+        (event h of the table is hypothesis h), by chr_library_loglike's rule
+        (include/chroma_amd.h): a LogLikelihood.  n: the observed photo-electron counts
+        per channel (or 0 / 1 for mode='hit'); t: the observed times of the hit channels,
+        or None for no time term; both numpy arrays or device arrays (a Sampled's n and t
+        of one event are used without a download).  floor: the expected noise charge per
+        channel; tfloor: the noise time density, by default floor / (t_hi - t_lo) of the
+        library's histogram.  The Poisson form leaves out lgamma(n + 1), which no
+        hypothesis changes.  Asynchronous on the current stream; `last_loglike_path`
+        records the path taken (NARROW or WIDE)."""
+        from chroma.gpu import gpuarray as ga
+        from chroma.gpu.tools import current_stream
+        observed, obs = self._observed(n, t, mode, floor, tfloor)
+        keep, desc = self._upload_entries(entries)
+        count = max(entries.nevents, 1)
+        words, bad = ga.empty(count, np.int64), ga.empty(count, np.uint32)
+        skipped = ga.zeros(1, np.uint64)
+        if entries.nevents > 0:
+            _native.call('chr_library_loglike', ctypes.byref(self._desc()), ctypes.byref(desc), ctypes.byref(obs),
+                         words.gpudata, bad.gpudata, skipped.gpudata, current_stream())
+            self.last_loglike_path = int(_native.lib().chr_library_loglike_last_path())
+        out = LogLikelihood(entries.nevents, words[:entries.nevents], bad[:entries.nevents], skipped,
+                            lambda a: a.get())
+        out._keep = (keep, observed)       # the device arrays the launch reads, until it has run
+        return out
+
     def sample(self, entries, rng_states):
         """Sampled charge and time per event and channel, drawn from rng_states
         (chroma.gpu.get_rng_states), which advance; asynchronous on the current stream."""
@@ -256,6 +348,19 @@ class HostPhotonLibrary(_Library):
         _native.call('chr_library_expect_host', ctypes.byref(self._desc()), ctypes.byref(desc), mu.ctypes.data,
                      None if tfirst is None else tfirst.ctypes.data, skipped.ctypes.data)
         return Expected(entries.nevents, self.nchannels, mu, tfirst, skipped, lambda a: a)
+
+    _observed_array = _Library._host_observed_array
+
+    def log_likelihood(self, entries, n, t=None, mode='poisson', floor=1e-3, tfloor=None):
+        """GPUPhotonLibrary.log_likelihood over host arrays (chr_library_loglike_host)."""
+        observed, obs = self._observed(n, t, mode, floor, tfloor)
+        desc = self._entries_desc(entries)
+        words, bad = np.zeros(entries.nevents, np.int64), np.zeros(entries.nevents, np.uint32)
+        skipped = np.zeros(1, np.uint64)
+        if entries.nevents > 0:
+            _native.call('chr_library_loglike_host', ctypes.byref(self._desc()), ctypes.byref(desc), ctypes.byref(obs),
+                         words.ctypes.data, bad.ctypes.data, skipped.ctypes.data)
+        return LogLikelihood(entries.nevents, words, bad, skipped, lambda a: a)
 
     def sample(self, entries, rng_states):
         if not (isinstance(rng_states, np.ndarray) and rng_states.dtype == np.uint32 and rng_states.flags.c_contiguous

@@ -1,17 +1,21 @@
 // library.h -- the photon-library lookup (include/chroma_amd.h, "photon library"):
 // what one (event, channel) pair takes from one entry of the event, for the
 // expected values (chr_library_expect) and for the sampled channels
-// (chr_library_sample), decided by one text for the gfx950 kernels (library.hip)
-// and for the host twins (library_host.cpp, the host compiler).  CHR_FN code over
-// chroma_fmath.h and chroma_rng.h only; every multiply-add is an explicit
-// chr_fmaf and both sides are built with -ffp-contract=off, so the device, the
-// host twin and the numpy restatement (tests/library_model.py) give the same words.
+// (chr_library_sample), and what a channel adds to the log-likelihood of an
+// observed event under a hypothesis (chr_library_loglike), decided by one text
+// for the gfx950 kernels (library.hip) and for the host twins (library_host.cpp,
+// the host compiler).  CHR_FN code over chroma_fmath.h and chroma_rng.h (and
+// hitmap.h's time bin) only; every multiply-add is an explicit chr_fmaf and both
+// sides are built with -ffp-contract=off, so the device, the host twin and the
+// numpy restatements (tests/library_model.py, tests/loglike_model.py) give the
+// same words.
 #ifndef CHROMA_LIBRARY_H
 #define CHROMA_LIBRARY_H
 
 #include "../../include/chroma_amd.h"
 #include "../../include/chroma_fmath.h"
 #include "../../include/chroma_rng.h"
+#include "hitmap.h"
 
 #define CHR_LIBRARY_NO_KEY 0xFFFFFFFFu      /* CHR_HITMAP_NO_KEY: the cleared tmin word */
 #define CHR_LIBRARY_POISSON_SPLIT 32.0f     /* below: Knuth's product; from here on: the normal form */
@@ -119,14 +123,64 @@ CHR_FN void chr_library_sample_pair(const chr_library_map *lib, const uint32_t *
     *t_out = n == 0u ? CHR_LIBRARY_NO_HIT_TIME : (lib->ntbins ? tdrawn : tfirst);
 }
 
+// ---------------------------------------------------------------- the log-likelihood rule
+#define CHR_LOGLIKE_LIMIT 8388608.0f        /* 2^23: a channel's term is clamped to +-LIMIT */
+#define CHR_LOGLIKE_SCALE 1048576.0f        /* 2^20: the fixed-point unit of a word */
+#define CHR_LOGLIKE_MAX_CHANNELS 0x100000u  /* 2^20 words of at most 2^43 each fit an int64 */
+
+// log-likelihood step 1, the time part: the histogram bin of the observed time tobs for an
+// entry made at t (the hit map's own bin function), -1 when there is none
+CHR_FN int32_t chr_library_loglike_bin(const chr_library_map *lib, float tobs, float t) {
+    return chr_hitmap_time_bin(tobs - t, lib->t_lo, lib->inv, lib->ntbins);
+}
+
+// log-likelihood step 1, the time part: one counted entry's histogram word h of the bin found
+CHR_FN void chr_library_loglike_time_step(float w, uint32_t h, float *a) { *a = chr_fmaf(w, (float)h, *a); }
+
+// log-likelihood steps 2-4: the channel's term from mu, the time fold a (0 without tobs) and
+// the observed n and tobs; `timed`: tobs was given
+CHR_FN float chr_library_loglike_term(float mu, float a, uint32_t n, int timed, float tobs, uint32_t mode,
+                                      float floor, float tfloor, float inv) {
+    const float m = mu + floor;
+    if (!(m > 0.0f)) return n == 0u ? 0.0f : -CHR_LOGLIKE_LIMIT;
+    if (n == 0u) return -m;
+    float term;
+    if (mode == 0u) {
+        term = chr_fmaf((float)n, chr_logf(m), -m);
+    } else {
+        const float p = 1.0f - chr_expf(-m);
+        term = p > 0.0f ? chr_logf(p) : -CHR_LOGLIKE_LIMIT;
+    }
+    if (timed && !chr_isnan(tobs)) {
+        const float d = chr_fmaf(a, inv, tfloor);
+        term = (term + (d > 0.0f ? chr_logf(d) : -CHR_LOGLIKE_LIMIT)) - chr_logf(m);
+    }
+    return term;
+}
+
+// log-likelihood step 5: the fixed-point word of a term; a NaN gives 0 and counts in *bad
+CHR_FN int64_t chr_library_loglike_word(float term, uint32_t *bad) {
+    if (chr_isnan(term)) {
+        *bad += 1u;
+        return 0;
+    }
+    if (term > CHR_LOGLIKE_LIMIT) term = CHR_LOGLIKE_LIMIT;
+    if (term < -CHR_LOGLIKE_LIMIT) term = -CHR_LOGLIKE_LIMIT;
+    return (int64_t)(term * CHR_LOGLIKE_SCALE);                   // |product| <= 2^43, exact
+}
+
 #ifdef __cplusplus
 namespace chr {
-// The refusals the four entry points share (library_host.cpp), made before anything is
+// The refusals the entry points share (library_host.cpp), made before anything is
 // read through a pointer; fills *lib.  rng: chr_library_sample's states, checked when
 // `sampling`.
 int library_check(const char *who, const chr_hitmap_desc *desc, const chr_library_entries *entries, const void *out_a,
                   const void *out_b, const void *skipped, int sampling, const void *rng, uint32_t nslots,
                   chr_library_map *lib);
+// library_check and what chr_library_loglike refuses beyond it
+int library_loglike_check(const char *who, const chr_hitmap_desc *desc, const chr_library_entries *hyp,
+                          const chr_library_observed *obs, const void *ll, const void *bad, const void *skipped,
+                          chr_library_map *lib);
 }  // namespace chr
 #endif
 

@@ -1,4 +1,5 @@
-// library.hip -- gfx950 photon-library lookup (chr_library_expect, chr_library_sample).
+// library.hip -- gfx950 photon-library lookup (chr_library_expect, chr_library_sample,
+// chr_library_loglike).
 //
 // expect   the hot path: per event, the rows counts[s, :] (and tmin[s, :]) of its
 //          entries' sources are gathered and folded, channel by channel, into mu and
@@ -23,6 +24,11 @@
 // sample   one work-item per rng slot walks its pairs j, j + T, ... in ascending order
 //          through library.h's chr_library_sample_pair: the draw counts differ from
 //          pair to pair, so there is nothing to share between lanes.
+// loglike  expect's structure with another ending: instead of storing mu, each lane
+//          turns its channels' mu (and, with observed times, the histogram words
+//          gathered on the way) into fixed-point words, which are summed as integers
+//          over the wave, the workgroup (LDS) and the channel tiles (one 64-bit atomic
+//          per workgroup and hypothesis); see loglike_kernel.
 //
 // All loops are bounded by the table; no workgroup waits for another.
 #include <hip/hip_runtime.h>
@@ -58,9 +64,20 @@ template <> struct Words<4> { typedef uint4 u; typedef float4 f; };
 __device__ __forceinline__ uint32_t word_of(const uint32_t &v, int) { return v; }
 __device__ __forceinline__ uint32_t word_of(const uint4 &v, int j) { return j == 0 ? v.x : j == 1 ? v.y : j == 2 ? v.z : v.w; }
 
+// slot u's row from its source word s (`have`: the slot is an entry): the source, or row 0 for a source that
+// is none; counts the entry in nskipped then, and sets bit u of `known` for an entry of a source that exists
+__device__ __forceinline__ uint32_t row_of(const chr_library_map &lib, uint32_t s, bool have, int u, uint32_t &known,
+                                           uint32_t &nskipped) {
+    const bool is_source = s < lib.nsources;
+    if (have && !is_source) nskipped += 1u;
+    if (have && is_source) known |= 1u << u;
+    return is_source ? s : 0u;
+}
+
 // The rows of entries i .. i + U - 1 of the non-empty range [first, last), the same in every lane: the
 // entry's source, or row 0 for a source that is none and for a slot past the end (which reads the last
 // entry, so no index leaves the range).  Bit u of `known`: the slot is an entry of a source that exists.
+// Each source is pinned to a scalar register as it arrives.
 template <int U>
 __device__ __forceinline__ void load_rows(const chr_library_map &lib, const Entries &en, uint32_t i, uint32_t last,
                                           uint32_t (&row)[U], uint32_t &known, uint32_t &nskipped) {
@@ -68,11 +85,7 @@ __device__ __forceinline__ void load_rows(const chr_library_map &lib, const Entr
 #pragma unroll
     for (int u = 0; u < U; ++u) {
         const bool have = i + u < last;
-        const uint32_t s = uniform_u32(en.source[have ? i + u : last - 1u]);
-        const bool is_source = s < lib.nsources;
-        if (have && !is_source) nskipped += 1u;
-        row[u] = is_source ? s : 0u;
-        if (have && is_source) known |= 1u << u;
+        row[u] = row_of(lib, uniform_u32(en.source[have ? i + u : last - 1u]), have, u, known, nskipped);
     }
 }
 
@@ -147,6 +160,166 @@ __global__ __launch_bounds__(BLOCK) void expect_kernel(chr_library_map lib, Entr
     }
 }
 
+struct Observed {
+    const uint32_t *nobs;
+    const float *tobs;
+    uint32_t mode;
+    float floor, tfloor;
+};
+
+__device__ __forceinline__ float word_of(const float &v, int) { return v; }
+__device__ __forceinline__ float word_of(const float4 &v, int j) { return j == 0 ? v.x : j == 1 ? v.y : j == 2 ? v.z : v.w; }
+
+// load_rows' rows and the entries' times, which the histogram gather's addresses wait for (slot u past the
+// end has the last entry's): every load of the group is requested before the first word is pinned to a
+// scalar register, so the group costs one round trip, not one per slot
+template <int U>
+__device__ __forceinline__ void load_rows_times(const chr_library_map &lib, const Entries &en, uint32_t i,
+                                                uint32_t last, uint32_t (&row)[U], float (&t)[U], uint32_t &known,
+                                                uint32_t &nskipped) {
+    uint32_t s[U];
+    float tv[U];
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+        const uint32_t at = i + u < last ? i + u : last - 1u;
+        s[u] = en.source[at];
+        tv[u] = en.t[at];
+    }
+    known = 0u;
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+        row[u] = row_of(lib, uniform_u32(s[u]), i + u < last, u, known, nskipped);
+        t[u] = uniform_f32(tv[u]);
+    }
+}
+
+// chr_library_loglike.  Lanes, grid and the entry groups as in expect_kernel (hypothesis = event).  The
+// tile's nobs / tobs are loaded once, ahead of the hypothesis loop.  A group's histogram words -- one per
+// (entry of a source that exists, channel with nobs > 0 whose time falls into a bin), the bin differing
+// from lane to lane -- are requested with the group's rows, their addresses being known from the times
+// fetched a group ago.  Each lane turns its channels' terms into words; the words (0 past nchannels) are
+// added over the wave with integer cross-lane adds, over the waves through LDS (two sets of slots used
+// in turn, so one barrier per hypothesis), and work-item 0 adds the workgroup's sum to ll[h] with one
+// 64-bit atomic; bad likewise.  Only integers cross lanes.
+template <int W, int U, bool TIMED>
+__global__ __launch_bounds__(BLOCK) void loglike_kernel(chr_library_map lib, Entries en, Observed ob,
+                                                        long long *__restrict__ ll_out,
+                                                        uint32_t *__restrict__ bad_out, u64 *skipped) {
+    typedef typename Words<W>::u UW;
+    typedef typename Words<W>::f FW;
+    constexpr int WAVES = BLOCK / 64;
+    __shared__ long long wave_ll[2][WAVES];
+    __shared__ uint32_t wave_bad[2][WAVES];
+    const uint32_t c0 = (blockIdx.x * BLOCK + threadIdx.x) * W;
+    const bool lane_in = c0 < lib.nchannels;                       // wide: nchannels % 4 == 0, so c0 + 3 is in too
+    const uint32_t cl = lane_in ? c0 : 0u;
+    uint32_t n[W];
+    float tobs[W];
+    {
+        const UW nw = *reinterpret_cast<const UW *>(ob.nobs + cl);
+        FW tw = {};
+        if (TIMED) tw = *reinterpret_cast<const FW *>(ob.tobs + cl);
+#pragma unroll
+        for (int j = 0; j < W; ++j) {
+            n[j] = lane_in ? word_of(nw, j) : 0u;                  // a lane past the row gathers nothing
+            tobs[j] = word_of(tw, j);
+        }
+    }
+    uint32_t slot = 0u, nskipped = 0u;                             // of all this workgroup's hypotheses: below 2^32 entries
+    for (uint32_t h = blockIdx.y; h < en.nevents; h += gridDim.y, slot ^= 1u) {
+        const uint32_t first = uniform_u32(en.offsets[h]), last = uniform_u32(en.offsets[h + 1]);
+        float mu[W], a[W];
+#pragma unroll
+        for (int j = 0; j < W; ++j) {
+            mu[j] = a[j] = 0.0f;
+            // the lane masks the observed words decide (n > 0, tobs a NaN) are made again for each hypothesis:
+            // kept across the loop, a dozen 64-bit masks are more than the scalar registers hold
+            asm volatile("" : "+v"(n[j]), "+v"(tobs[j]));
+        }
+        uint32_t cur[U] = {}, next[U] = {}, cur_known = 0u, next_known = 0u;
+        float tcur[U] = {}, tnext[U] = {};
+        if (first < last) load_rows_times<U>(lib, en, first, last, cur, tcur, cur_known, nskipped);
+        for (uint32_t i = first; i < last; i += U) {
+            UW k[U];
+            uint32_t hw[U][W], binned = 0u;                        // bit u * W + j: hw[u][j] is a bin's word
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+                const size_t word = (size_t)cur[u] * lib.nchannels + cl;
+                k[u] = *reinterpret_cast<const UW *>(lib.counts + word);
+                if (TIMED) {
+#pragma unroll
+                    for (int j = 0; j < W; ++j) {
+                        hw[u][j] = 0u;
+                        if ((cur_known >> u & 1u) && n[j] > 0u) {
+                            const int32_t b = chr_library_loglike_bin(&lib, tobs[j], tcur[u]);
+                            if (b >= 0) {
+                                hw[u][j] = lib.thist[(word + j) * lib.ntbins + (uint32_t)b];
+                                binned |= 1u << (u * W + j);
+                            }
+                        }
+                    }
+                }
+            }
+            float w[U];
+            uint32_t ok = 0u;
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+                const uint32_t at = i + u < last ? i + u : last - 1u;
+                const uint32_t lo = uniform_u32((uint32_t)lib.emitted[cur[u]]);
+                const uint32_t hi = uniform_u32((uint32_t)(lib.emitted[cur[u]] >> 32));
+                const uint64_t em = ((uint64_t)hi << 32) | lo;
+                if ((cur_known >> u & 1u) && em != 0u) ok |= 1u << u;
+                w[u] = chr_library_weight(uniform_u32(en.nphotons[at]), em != 0u ? em : 1u);
+            }
+            if (i + U < last) load_rows_times<U>(lib, en, i + U, last, next, tnext, next_known, nskipped);
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+                if (ok >> u & 1u) {
+#pragma unroll
+                    for (int j = 0; j < W; ++j) {
+                        float no_time = 0.0f;
+                        chr_library_expect_step(w[u], tcur[u], word_of(k[u], j), CHR_LIBRARY_NO_KEY, &mu[j], &no_time);
+                        if (TIMED && (binned >> (u * W + j) & 1u)) chr_library_loglike_time_step(w[u], hw[u][j], &a[j]);
+                    }
+                }
+                cur[u] = next[u];
+                tcur[u] = tnext[u];
+            }
+            cur_known = next_known;
+        }
+        long long q = 0;
+        uint32_t bad = 0u;
+        if (lane_in) {
+#pragma unroll
+            for (int j = 0; j < W; ++j)
+                q += chr_library_loglike_word(chr_library_loglike_term(mu[j], a[j], n[j], TIMED, tobs[j], ob.mode,
+                                                                       ob.floor, ob.tfloor, lib.inv), &bad);
+        }
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) {
+            q += __shfl_xor(q, off);
+            bad += __shfl_xor(bad, off);
+        }
+        if ((threadIdx.x & 63u) == 0u) {
+            wave_ll[slot][threadIdx.x >> 6] = q;
+            wave_bad[slot][threadIdx.x >> 6] = bad;
+        }
+        __syncthreads();                                           // h depends on blockIdx alone: every wave arrives
+        if (threadIdx.x == 0) {
+            long long sum = 0;
+            uint32_t nbad = 0u;
+#pragma unroll
+            for (int v = 0; v < WAVES; ++v) {
+                sum += wave_ll[slot][v];
+                nbad += wave_bad[slot][v];
+            }
+            if (sum) atomicAdd(reinterpret_cast<u64 *>(ll_out + h), (u64)sum);
+            if (nbad) atomicAdd(bad_out + h, nbad);
+        }
+    }
+    if (blockIdx.x == 0 && threadIdx.x == 0 && nskipped) atomicAdd(skipped, (u64)nskipped);
+}
+
 // work-item j < T: rng slot j, pairs j, j + T, ...
 __global__ __launch_bounds__(BLOCK) void sample_kernel(chr_library_map lib, Entries en, uint32_t *rng_states,
                                                        uint32_t nslots, uint32_t T, uint32_t npairs, uint32_t *n_out,
@@ -180,15 +353,36 @@ Entries entries_of(const chr_library_entries *en) {
 
 bool aligned16(const void *p) { return ((uintptr_t)p & 15u) == 0; }
 
+bool narrow_forced() {
+    const char *e = getenv("CHR_LIBRARY_PATH");
+    return e && e[0] == 'n';
+}
+
 // CHR_LIBRARY_PATH=n forces the narrow path (A/B, tests); the wide one needs its alignment
 bool use_wide(const chr_library_map &lib, const float *mu, const float *tfirst) {
     if (lib.nchannels % 4u != 0u || !aligned16(lib.counts) || !aligned16(mu)) return false;
     if (lib.tmin && (!aligned16(lib.tmin) || !aligned16(tfirst))) return false;
-    const char *e = getenv("CHR_LIBRARY_PATH");
-    return !(e && e[0] == 'n');
+    return !narrow_forced();
 }
 
-thread_local int last_path = -1;
+// with observed times the call is bound by the histogram gather, one word per (entry, hit channel) whatever
+// the lane's width, and four channels per lane only cost workgroups: the wide path is for calls without times
+bool loglike_wide(const chr_library_map &lib, const chr_library_observed *obs) {
+    if (obs->tobs || lib.nchannels % 4u != 0u || !aligned16(lib.counts) || !aligned16(obs->nobs)) return false;
+    return !narrow_forced();
+}
+
+thread_local int last_path = -1, loglike_last_path = -1;
+
+template <int W, int U, bool TIMED>
+void launch_loglike(const chr_library_map &lib, const chr_library_entries *hyp, const chr_library_observed *obs,
+                    int64_t *ll, uint32_t *bad, u64 *skipped, hipStream_t stream) {
+    const uint32_t per_wg = BLOCK * W;
+    const dim3 grid((lib.nchannels + per_wg - 1) / per_wg, std::min(hyp->nevents, MAX_GRID_Y));
+    const Observed ob{obs->nobs, obs->tobs, obs->mode, obs->floor, obs->tfloor};
+    hipLaunchKernelGGL((loglike_kernel<W, U, TIMED>), grid, dim3(BLOCK), 0, stream, lib, entries_of(hyp), ob,
+                       (long long *)ll, bad, skipped);
+}
 
 template <int W, int U>
 void launch_expect(const chr_library_map &lib, const chr_library_entries *en, float *mu, float *tfirst, u64 *skipped,
@@ -221,6 +415,27 @@ extern "C" int chr_library_expect(const chr_hitmap_desc *desc, const chr_library
 }
 
 extern "C" int chr_library_last_path(void) { return last_path; }
+
+extern "C" int chr_library_loglike(const chr_hitmap_desc *desc, const chr_library_entries *hyp,
+                                   const chr_library_observed *obs, int64_t *d_ll, uint32_t *d_bad,
+                                   uint64_t *d_skipped, void *stream) {
+    chr_library_map lib;
+    CHR_TRY(chr::library_loglike_check("chr_library_loglike", desc, hyp, obs, d_ll, d_bad, d_skipped, &lib));
+    if (hyp->nevents == 0) return CHR_OK;
+    CHR_HIP_CHECK(hipMemsetAsync(d_ll, 0, sizeof(int64_t) * (size_t)hyp->nevents, (hipStream_t)stream));
+    CHR_HIP_CHECK(hipMemsetAsync(d_bad, 0, sizeof(uint32_t) * (size_t)hyp->nevents, (hipStream_t)stream));
+    const bool wide = loglike_wide(lib, obs);
+    // with times, half the entries per group: each brings its histogram words, and the scalar registers are few
+    if (wide) launch_loglike<4, UNROLL_WIDE, false>(lib, hyp, obs, d_ll, d_bad, (u64 *)d_skipped, (hipStream_t)stream);
+    else if (obs->tobs)
+        launch_loglike<1, UNROLL_NARROW / 2, true>(lib, hyp, obs, d_ll, d_bad, (u64 *)d_skipped, (hipStream_t)stream);
+    else launch_loglike<1, UNROLL_NARROW, false>(lib, hyp, obs, d_ll, d_bad, (u64 *)d_skipped, (hipStream_t)stream);
+    CHR_HIP_CHECK(hipGetLastError());
+    loglike_last_path = wide ? 1 : 0;
+    return CHR_OK;
+}
+
+extern "C" int chr_library_loglike_last_path(void) { return loglike_last_path; }
 
 extern "C" int chr_library_sample(const chr_hitmap_desc *desc, const chr_library_entries *entries,
                                   uint32_t *d_rng_states, uint32_t nslots, uint32_t *d_n, float *d_t,

@@ -1,7 +1,7 @@
 // library_host.cpp -- the host side of the photon-library lookup: the refusals
 // shared with the device entries (library.hip) and the host twins
-// chr_library_expect_host / chr_library_sample_host (library.h's rule built by
-// the host compiler: the device's words without a GPU).
+// chr_library_expect_host / chr_library_sample_host / chr_library_loglike_host
+// (library.h's rules built by the host compiler: the device's words without a GPU).
 #include <cstdint>
 
 #include "common.h"
@@ -37,6 +37,23 @@ int chr::library_check(const char *who, const chr_hitmap_desc *desc, const chr_l
         return chr::fail(CHR_ERR_INVALID, "%s: null argument", who);
     *lib = chr_library_map{desc->nsources, (uint32_t)desc->nchannels, desc->ntbins, desc->t_lo, desc->inv,
                            desc->d_emitted, desc->d_counts, desc->d_tmin, desc->d_thist};
+    return CHR_OK;
+}
+
+int chr::library_loglike_check(const char *who, const chr_hitmap_desc *desc, const chr_library_entries *hyp,
+                               const chr_library_observed *obs, const void *ll, const void *bad, const void *skipped,
+                               chr_library_map *lib) {
+    // bad stands where expect's tfirst does, and is required whether or not the library keeps tmin
+    if (!obs || !obs->nobs || !bad) return chr::fail(CHR_ERR_INVALID, "%s: null argument", who);
+    CHR_TRY(chr::library_check(who, desc, hyp, ll, bad, skipped, 0, nullptr, 0, lib));
+    if (obs->mode > 1u) return chr::fail(CHR_ERR_INVALID, "%s: mode %u is neither 0 (Poisson) nor 1 (hit)", who, obs->mode);
+    if (!(obs->floor >= 0.0f) || !(obs->tfloor >= 0.0f))
+        return chr::fail(CHR_ERR_INVALID, "%s: floor = %g and tfloor = %g must not be negative or NaN", who,
+                         (double)obs->floor, (double)obs->tfloor);
+    if (obs->tobs && !desc->d_thist)
+        return chr::fail(CHR_ERR_INVALID, "%s: observed times but the library keeps no histogram", who);
+    if ((uint32_t)desc->nchannels > CHR_LOGLIKE_MAX_CHANNELS)
+        return chr::fail(CHR_ERR_INVALID, "%s: %d channels exceed 2^20", who, desc->nchannels);
     return CHR_OK;
 }
 
@@ -101,5 +118,41 @@ extern "C" int chr_library_sample_host(const chr_hitmap_desc *desc, const chr_li
         st[3 * (size_t)nslots + j] = rng.v2; st[4 * (size_t)nslots + j] = rng.v3; st[5 * (size_t)nslots + j] = rng.v4;
     }
     *h_skipped += skipped_entries(lib, entries);
+    return CHR_OK;
+}
+
+extern "C" int chr_library_loglike_host(const chr_hitmap_desc *desc, const chr_library_entries *hyp,
+                                        const chr_library_observed *obs, int64_t *h_ll, uint32_t *h_bad,
+                                        uint64_t *h_skipped) {
+    chr_library_map lib;
+    CHR_TRY(chr::library_loglike_check("chr_library_loglike_host", desc, hyp, obs, h_ll, h_bad, h_skipped, &lib));
+    if (hyp->nevents == 0) return CHR_OK;
+    CHR_TRY(check_offsets("chr_library_loglike_host", hyp));
+    const int timed = obs->tobs != nullptr;
+    for (uint32_t h = 0; h < hyp->nevents; ++h) {
+        int64_t ll = 0;
+        uint32_t bad = 0;
+        for (uint32_t c = 0; c < lib.nchannels; ++c) {
+            const uint32_t n = obs->nobs[c];
+            const float tobs = timed ? obs->tobs[c] : 0.0f;
+            float mu = 0.0f, a = 0.0f, unused = 0.0f;
+            for (uint32_t i = hyp->offsets[h]; i < hyp->offsets[h + 1]; ++i) {
+                const uint32_t s = hyp->source[i];
+                if (s >= lib.nsources || lib.emitted[s] == 0u) continue;
+                const float w = chr_library_weight(hyp->nphotons[i], lib.emitted[s]);
+                const size_t word = (size_t)s * lib.nchannels + c;
+                chr_library_expect_step(w, hyp->t[i], lib.counts[word], CHR_LIBRARY_NO_KEY, &mu, &unused);
+                if (timed && n > 0u) {
+                    const int32_t b = chr_library_loglike_bin(&lib, tobs, hyp->t[i]);
+                    if (b >= 0) chr_library_loglike_time_step(w, lib.thist[word * lib.ntbins + (uint32_t)b], &a);
+                }
+            }
+            ll += chr_library_loglike_word(
+                chr_library_loglike_term(mu, a, n, timed, tobs, obs->mode, obs->floor, obs->tfloor, lib.inv), &bad);
+        }
+        h_ll[h] = ll;
+        h_bad[h] = bad;
+    }
+    *h_skipped += skipped_entries(lib, hyp);
     return CHR_OK;
 }

@@ -792,6 +792,72 @@ int chr_library_expect_host(const chr_hitmap_desc *lib, const chr_library_entrie
 int chr_library_sample_host(const chr_hitmap_desc *lib, const chr_library_entries *entries, uint32_t *h_rng_states,
                             uint32_t nslots, uint32_t *h_n, float *h_t, uint64_t *h_skipped);
 
+/* Log-likelihood: the way back.  One observed event (nobs, optional tobs) is
+ * scored against many hypotheses straight from the library; hypothesis h is
+ * "event" h of a chr_library_entries table, and eight bytes per hypothesis are
+ * written.  The rule (csrc/library.h, one text for the device, the host twin
+ * and, restated, tests/loglike_model.py), LIMIT = 8388608.0f (2^23), for
+ * hypothesis h and channel c, in this order:
+ *   1. mu exactly as steps 1-4 of the expected values: the same w, the same
+ *      fmaf fold in entry order, so mu is the word chr_library_expect stores.
+ *      With tobs given and nobs[c] > 0, also a = 0.0f folded over the same
+ *      counted entries: b = the hit map's time bin (rule step 6 there) of
+ *      tobs[c] - t[i], one float32 subtract; b >= 0:
+ *      a = fmaf(w, (float)thist[(s*nchannels + c)*ntbins + b], a).
+ *   2. m = mu + floor, one float32 add; n = nobs[c].
+ *   3. the charge term:
+ *        !(m > 0) (zero, negative, NaN):  term = n == 0 ? 0.0f : -LIMIT
+ *        n == 0:                          term = -m
+ *        mode 0 (Poisson):                term = fmaf((float)n, chr_logf(m), -m)
+ *        mode 1 (hit / no hit):           p = 1.0f - chr_expf(-m);
+ *                                         term = p > 0 ? chr_logf(p) : -LIMIT
+ *      The Poisson form's lgamma(n + 1) is the same for every hypothesis and
+ *      is LEFT OUT: ll is the log-likelihood up to that constant.
+ *   4. the time term, only with tobs given, n > 0, m > 0 and tobs[c] not NaN:
+ *      d = fmaf(a, inv, tfloor);
+ *      term = (term + (d > 0 ? chr_logf(d) : -LIMIT)) - chr_logf(m), two
+ *      float32 operations in that order: the single-photon arrival density of
+ *      the mixture "library signal plus flat noise", normalised when tfloor =
+ *      floor / (t_hi - t_lo).
+ *   5. the word: a NaN term gives q = 0 and adds 1 to bad[h]; otherwise the
+ *      term is clamped to [-LIMIT, LIMIT] and q = (int64_t)(term *
+ *      1048576.0f), truncated toward zero (the product is exact).
+ *   6. ll[h] += q, a 64-bit INTEGER add.
+ * A sum of integers does not depend on how the channels are spread over
+ * lanes, waves and workgroups, so ll and bad are functions of the inputs
+ * alone, bit for bit (as a hit map is).  |q| <= 2^43 and nchannels <= 2^20, so
+ * the sum cannot overflow; ll[h] / 2^20 is the log-likelihood, resolved to
+ * 1e-6 per channel.  An entry of a source >= nsources adds nothing and is
+ * counted once in *skipped, as in chr_library_expect. */
+typedef struct chr_library_observed {
+    const uint32_t *nobs;   /* nchannels: photo-electron counts, or 0 / 1 for hit / no hit */
+    const float *tobs;      /* nchannels: the time of a hit channel; or NULL: no time term */
+    uint32_t mode;          /* 0 Poisson, 1 hit / no hit */
+    float floor, tfloor;    /* expected noise charge per channel; noise time density (read with tobs) */
+} chr_library_observed;
+/* d_ll[nevents] (int64) and d_bad[nevents] (u32) are WRITTEN: they are zeroed on
+ * `stream` before the kernel; *d_skipped (u64) is ADDED to.  Two paths with
+ * identical words: wide (4 channels per lane; tobs NULL, nchannels a multiple
+ * of 4 and counts, nobs 16-byte aligned) and narrow (always with tobs, where
+ * the histogram gather decides the time); the environment's
+ * CHR_LIBRARY_PATH=n forces the narrow one.  CHR_ERR_INVALID before anything is
+ * read through a pointer for everything chr_library_expect refuses of the
+ * library and the table (nevents * nchannels > 2^31 among it: inherited, so
+ * that one check serves every entry; this call writes 12 bytes per hypothesis
+ * and has no table of that size -- split larger tables), and for: a null obs, nobs, d_ll or d_bad; mode > 1;
+ * floor or tfloor NaN or negative; tobs non-null while the library keeps no
+ * thist; nchannels > 2^20.  nevents == 0 is CHR_OK and touches nothing.  Async
+ * on `stream`. */
+int chr_library_loglike(const chr_hitmap_desc *lib, const chr_library_entries *hyp, const chr_library_observed *obs,
+                        int64_t *d_ll, uint32_t *d_bad, uint64_t *d_skipped, void *stream);
+/* The path of the calling thread's last chr_library_loglike that launched:
+ * 0 narrow, 1 wide, -1 none yet. */
+int chr_library_loglike_last_path(void);
+/* The same on the host (every pointer addresses HOST memory), word-identical,
+ * with the same refusals and one more: offsets not ascending. */
+int chr_library_loglike_host(const chr_hitmap_desc *lib, const chr_library_entries *hyp,
+                             const chr_library_observed *obs, int64_t *h_ll, uint32_t *h_bad, uint64_t *h_skipped);
+
 /* ------------------------------------------------------------------- PDF
  * replaces: chroma/cuda/pdf.cu, launched by GPUPDF / GPUKernelPDF
  * (chroma/gpu/pdf.py:7-372).  Inputs are GPUChannels words (t, q: f32; DAQ
