@@ -146,6 +146,7 @@ _SIGNATURES = {
     'chr_distance_to_mesh': (c_i32, [c_vp, c_u32, c_vp, c_vp, c_vp, c_vp]),
     'chr_kernel_info': (c_i32, [c_i32, ctypes.POINTER(KernelAttr)]),
     'chr_selftest_linalg': (c_i32, [c_i32, c_u32, c_vp, c_vp, c_f32, c_vp, c_vp]),
+    'chr_selftest_fmath': (c_i32, [c_i32, c_u32, c_vp, c_vp, c_vp, c_vp]),
     'chr_selftest_rotate': (c_i32, [c_u32, c_vp, c_vp, c_f32, c_f32, c_f32, c_vp, c_vp]),
     'chr_selftest_sample_cdf': (c_i32, [c_u32, c_vp, c_u32, c_i32, c_vp, c_vp, c_f32, c_f32, c_i32, c_vp, c_vp]),
     'chr_unique_vertices': (c_i32, [c_vp, c_u64, c_vp, ctypes.POINTER(c_u64), c_vp]),

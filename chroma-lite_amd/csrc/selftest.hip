@@ -55,6 +55,36 @@ __global__ __launch_bounds__(TB) void linalg_kernel(int op, uint32_t n, const fl
     }
 }
 
+// include/chroma_fmath.h, one function per launch, and the IEEE primitives it is built from (sqrt, fma,
+// division as this library's flags compile them); the result's bit pattern.  The oracle's math_bits is
+// the same switch on the host.
+__global__ __launch_bounds__(TB) void fmath_kernel(int op, uint32_t n, const float *X, const float *Y, uint32_t *out) {
+    const uint32_t i = blockIdx.x * TB + threadIdx.x;
+    if (i >= n) return;
+    const float x = X[i], y = Y[i];
+    uint32_t r = 0u;
+    switch (op) {
+        case CHR_FMATH_LOG: r = chr_f2u(chr_logf(x)); break;
+        case CHR_FMATH_EXP: r = chr_f2u(chr_expf(x)); break;
+        case CHR_FMATH_SIN: r = chr_f2u(chr_sinf(x)); break;
+        case CHR_FMATH_COS: r = chr_f2u(chr_cosf(x)); break;
+        case CHR_FMATH_TAN: r = chr_f2u(chr_tanf(x)); break;
+        case CHR_FMATH_ASIN: r = chr_f2u(chr_asinf(x)); break;
+        case CHR_FMATH_ACOS: r = chr_f2u(chr_acosf(x)); break;
+        case CHR_FMATH_ATAN2: r = chr_f2u(chr_atan2f(y, x)); break;
+        case CHR_FMATH_ATAN: r = chr_f2u(chr_atanf(x)); break;
+        case CHR_FMATH_ERF: r = chr_f2u(chr_erff(x)); break;
+        case CHR_FMATH_LDEXP: r = chr_f2u(chr_ldexpf(x, CHR_FMATH_LDEXP_K(y))); break;
+        case CHR_FMATH_SAT_U32: r = chr_sat_u32(x); break;
+        case CHR_FMATH_RINT_SMALL: r = chr_f2u(chr_rintf_small(x)); break;
+        case CHR_FMATH_SQRT: r = chr_f2u(chr_sqrtf(x)); break;
+        case CHR_FMATH_FMA: r = chr_f2u(chr_fmaf(x, y, x)); break;
+        case CHR_FMATH_DIV: r = chr_f2u(x / y); break;
+        default: break;
+    }
+    out[i] = r;
+}
+
 // test/rotate_test.cu
 __global__ __launch_bounds__(TB) void rotate_kernel(uint32_t n, const float *A, const float *phi, V3 axis, float *out) {
     const uint32_t i = blockIdx.x * TB + threadIdx.x;
@@ -88,6 +118,17 @@ extern "C" int chr_selftest_linalg(int32_t op, uint32_t n, const float *d_a, con
     if (!d_a || !d_b || !d_out) return chr::fail(CHR_ERR_INVALID, "chr_selftest_linalg: null argument");
     hipLaunchKernelGGL(chr::linalg_kernel, dim3(chr::blocks(n)), dim3(chr::TB), 0, (hipStream_t)stream, op, n, d_a, d_b,
                        c, d_out);
+    CHR_HIP_CHECK(hipGetLastError());
+    return CHR_OK;
+}
+
+extern "C" int chr_selftest_fmath(int32_t op, uint32_t n, const float *d_x, const float *d_y, uint32_t *d_out_bits,
+                                  void *stream) {
+    if (op < 0 || op >= CHR_FMATH_NOPS) return chr::fail(CHR_ERR_INVALID, "chr_selftest_fmath: unknown op %d", op);
+    if (n == 0) return CHR_OK;
+    if (!d_x || !d_y || !d_out_bits) return chr::fail(CHR_ERR_INVALID, "chr_selftest_fmath: null argument");
+    hipLaunchKernelGGL(chr::fmath_kernel, dim3(chr::blocks(n)), dim3(chr::TB), 0, (hipStream_t)stream, op, n, d_x, d_y,
+                       d_out_bits);
     CHR_HIP_CHECK(hipGetLastError());
     return CHR_OK;
 }

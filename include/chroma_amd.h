@@ -959,6 +959,28 @@ int chr_selftest_linalg(int32_t op, uint32_t n, const float *d_a, const float *d
 /* replaces: test/rotate_test.cu (rotate.h:21-28): d_out[i] = rotate(a[i], phi[i], n) */
 int chr_selftest_rotate(uint32_t n, const float *d_a, const float *d_phi, float nx, float ny, float nz,
                         float *d_out, void *stream);
+/* The functions of chroma_fmath.h and the IEEE primitives they rest on (sqrt, fma, plain
+ * division, each compiled with the library's own flags), one op per launch: the device side of
+ * the header's claim that gfx950 and the host oracle compute the same bits
+ * (tests/test_gpu_fmath.py; the oracle's orc_math_bits is the host side, same numbering). */
+enum chr_fmath_op {
+    CHR_FMATH_LOG = 0, CHR_FMATH_EXP, CHR_FMATH_SIN, CHR_FMATH_COS, CHR_FMATH_TAN, CHR_FMATH_ASIN, CHR_FMATH_ACOS,
+    CHR_FMATH_ATAN2,        /* chr_atan2f(y, x) */
+    CHR_FMATH_ATAN, CHR_FMATH_ERF,
+    CHR_FMATH_LDEXP,        /* chr_ldexpf(x, k), y carrying the integer k as a float (CHR_FMATH_LDEXP_K) */
+    CHR_FMATH_SAT_U32,      /* the result word is the integer itself */
+    CHR_FMATH_RINT_SMALL, CHR_FMATH_SQRT,
+    CHR_FMATH_FMA,          /* fma(x, y, x) */
+    CHR_FMATH_DIV,          /* x / y */
+    CHR_FMATH_NOPS
+};
+/* For this self test and its host twin (orc_math_bits) only, not for callers of the library: ldexp's
+ * exponent from its float carrier, a defined conversion for every y (0 outside +-4096 and for NaN) */
+#define CHR_FMATH_LDEXP_K(y) (((y) >= -4096.0f && (y) <= 4096.0f) ? (int)(y) : 0)
+/* d_out_bits[i] = the bit pattern of op(d_x[i], d_y[i]), i < n; one-argument ops read d_y too
+ * (any values).  Unknown op or null pointer: CHR_ERR_INVALID; n == 0 succeeds. */
+int chr_selftest_fmath(int32_t op, uint32_t n, const float *d_x, const float *d_y, uint32_t *d_out_bits,
+                       void *stream);
 /* replaces: test/test_sample_cdf.cu (random.h:27-55): one draw per slot i < n from
  * RNG slot state i (SoA, chr_init_rng layout; states are not written back);
  * uniform_grid = 0: sample_cdf(cdf_x, cdf_y), 1: sample_cdf(x0, delta, cdf_y),

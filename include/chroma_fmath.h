@@ -8,8 +8,24 @@
  * compute the SAME bits.  Both sides are compiled with -ffp-contract=off; every
  * fused multiply-add below is explicit (fmaf is exactly rounded on both).
  *
- * Accuracy: within ~2 ulp of the correctly-rounded result on the ranges the
- * propagator uses (tested in tests/test_fmath.py against float64 numpy).
+ * Accuracy, against float64 libm, as tests/test_fmath.py asserts it over the input sets of
+ * tests/fmath_cases.py (specials, every branch threshold +-64 floats, bit-pattern sweeps of each
+ * whole domain) and, where a maximum lives in a bounded range, over every float of that range
+ * (atan [0.25, 4), erf [0.5, 4), asin and acos [0.25, 1), sin and cos [0.25, pi/4], tan [0.25, 1.5],
+ * sin and cos (1e5, CHR_SINCOS_MAX]); the maximum measured and the argument that attains it in brackets:
+ *   chr_logf    <= 2 ulp (0.835 at 0x1.67cc32p+0); subnormal x <= 0.75 ulp (0.502 at 0x1.85569p-129)
+ *   chr_expf    <= 2 ulp; subnormal results, x in [-103.97, -87.34]: <= 0.75 of their 2^-149 spacing
+ *               (0.747 at -0x1.601e0ap+6, every float of the range tried)
+ *   chr_sinf    <= 0.75 ulp on [0, pi/4] (0.734 at 0x1.9205aap-1); absolute error by |x| below
+ *   chr_cosf    <= 1.25 ulp on [0, pi/4] (1.241 at 0x1.76e054p-1); absolute error by |x| below
+ *   chr_tanf    <= 4 ulp on [-1.5, 1.5] (3.232 at 0x1.51252ap+0)
+ *   chr_asinf   <= 2.5 ulp (2.350 at 0x1.0020a6p-1, just above the 0.5 branch), < 3e-7 absolute
+ *   chr_acosf   <= 1.5 ulp (1.282 at -0x1.007356p-1), < 5e-7 absolute
+ *   chr_atanf   <= 3 ulp (2.804 at 0x1.ba7036p-2, just above the tan(pi/8) branch), <= 1.4e-7 absolute
+ *   chr_atan2f  < 5e-7 absolute
+ *   chr_erff    <= 3.5e-7 absolute (3.488e-7 at 0x1.0990cap-1, just above the 0.5 branch)
+ * chr_sqrtf, chr_fmaf, + - * / and chr_ldexpf are correctly rounded (ldexp: one rounding, into the
+ * subnormals too); tests/test_gpu_fmath.py holds the device to that bit for bit.
  * Algorithms: classic Cody-Waite argument reduction + short minimax polynomials
  * (fdlibm/cephes-style public-domain coefficient sets).
  *
@@ -79,9 +95,14 @@ CHR_FN float chr_rintf_small(float x) {
     const float magic = 12582912.0f;
     return (x + magic) - magic;
 }
-/* x * 2^k for integer k (exact whenever the result is representable) */
+/* x * 2^k for integer k, rounded once (exact whenever the result is representable).  Up to three
+ * factors of 2^127 carry the smallest subnormal past the largest float, two of 2^-102 and one of
+ * 2^-126 the largest float to 0, so the clamps lose nothing.  (With one factor of 2^127 before its
+ * clamp, a subnormal x with k > 254 came back finite: found by tests/test_fmath.py against ldexpf;
+ * chr_expf, the only caller, stays at k <= 128.) */
 CHR_FN float chr_ldexpf(float x, int k) {
-    if (k > 127) { x *= chr_u2f(0x7f000000u); k -= 127; if (k > 127) k = 127; }
+    if (k > 127) { x *= chr_u2f(0x7f000000u); k -= 127;
+        if (k > 127) { x *= chr_u2f(0x7f000000u); k -= 127; if (k > 127) k = 127; } }
     else if (k < -126) { x *= chr_u2f(0x00800000u) * 16777216.0f; k += 102;  /* 2^-126 * 2^24 = 2^-102 */
         if (k < -126) { x *= chr_u2f(0x00800000u) * 16777216.0f; k += 102; if (k < -126) k = -126; } }
     return x * chr_u2f((uint32_t)(k + 127) << 23);
@@ -156,8 +177,28 @@ CHR_FN float chr_kcosf(float x) {   /* |x| <= pi/4 */
     float p = chr_fmaf(chr_fmaf(2.443315711809948e-5f, z, -1.388731625493765e-3f), z, 4.166664568298827e-2f);
     return chr_fmaf(z * z, p, chr_fmaf(-0.5f, z, 1.0f));
 }
+/* The domain of chr_sincosf (and chr_sinf, chr_cosf, chr_tanf): |x| <= CHR_SINCOS_MAX.
+ * chr_rem_pio2f takes n = chr_rintf_small(p) of the rounded product p = fl(x * two_over_pi), and
+ * chr_rintf_small is exact by its own condition for |p| < 2^22.  Below 2^22 the floats are 1/4 apart
+ * and a tie at 2^22 - 1/8 rounds up to the even 2^22, so p < 2^22 iff |x| * two_over_pi < 2^22 - 1/8,
+ * iff |x| < 6588397.386...; the largest float below that is 6588397 = 0x1.921fb4p+22 (floats are 1/2
+ * apart there: the next one, 6588397.5, gives p = 2^22), with p = 4194303.75 and n = 2^22.  It lies
+ * below 2^22 * pi/2 = 6588397.32 as well.  Beyond the limit, and for inf and NaN, both results are NaN: the
+ * same on every target and loud.  So n always fits an int, and no result exceeds 1 in magnitude.
+ * (Before the limit existed the reduction ran for every finite x: at 1e9 it returned 3.6e10 for a sine,
+ * and from 3.4e9 on (int)n was an out-of-range conversion that x86 and gfx950 resolve differently.)
+ * The three-term Cody-Waite reduction loses accuracy as n grows.  Largest absolute error of sin / cos
+ * against float64, by |x|, in units of 1e-8 (tests/test_fmath.py asserts each, rounded up):
+ *   (0,1e5] 9.3/9.4 (each decade asserted <= 10; every float of [1, 1e5] tried once: 9.30/9.31)
+ *   (1e5,1e6] 11.47 at 0x1.e62e28p+19 / 9.43 at 0x1.ee725p+17            (every float, asserted <= 12 / 10)
+ *   (1e6,CHR_SINCOS_MAX] 780.3 at 0x1.8f0bep+22 / 93.3 at 0x1.8d60c4p+22  (every float, asserted <= 781 / 94)
+ * i.e. within 1e-7 up to |x| = 1e5, 1.2e-7 up to 1e6 and up to 8e-6 from there to the limit.  For the
+ * thin-film model (propagate_complex), whose phase is two_ue = 4 pi Re(n2 cos2) thickness / wavelength:
+ * the phase stays in the 1e-7 regime while thickness / wavelength <= 1e5 / (4 pi Re(n2 cos2)), about
+ * 4e3 wavelengths (1.6 mm at 400 nm) for Re(n2 cos2) = 2, and the cosine becomes NaN from 66 times that on. */
+#define CHR_SINCOS_MAX 6588397.0f
 CHR_FN void chr_sincosf(float x, float *s, float *c) {
-    if (!chr_isfinite(x)) { *s = x - x; *c = x - x; return; }
+    if (!(chr_fabsf(x) <= CHR_SINCOS_MAX)) { *s = *c = chr_u2f(0x7fc00000u); return; }
     float r;
     int n = chr_rem_pio2f(x, &r);
     float sr = chr_ksinf(r), cr = chr_kcosf(r);
@@ -237,7 +278,8 @@ CHR_FN float chr_atan2f(float y, float x) {
  * Used by the kernel-density PDF normalisation (reference pdf.cu:311-362,
  * erff under --use_fast_math).  |x| < 0.5: Maclaurin series to x^13
  * (truncation < 5e-10 relative); 0.5 <= |x| < 4: Abramowitz & Stegun 7.1.26
- * (absolute error <= 1.5e-7; <= 2.5e-7 measured in float32); |x| >= 4: +-1.  Parity with CUDA's erff is
+ * (absolute error <= 1.5e-7 as a formula; in float32 <= 3.5e-7: 3.488e-7 at
+ * 0x1.0990cap-1, every float of [0.5, 4) tried, tests/test_fmath.py); |x| >= 4: +-1.  Parity with CUDA's erff is
  * unpinned (a few 1e-7 absolute), identical between HIP and the oracle. */
 CHR_FN float chr_erff(float x) {
     if (chr_isnan(x)) return x;

@@ -1279,21 +1279,35 @@ EXPORT int orc_fill_state(const chr_geometry_desc *d, const float *posdir, int32
     return 0;
 }
 
-/* math probes (tests/test_fmath.py) */
-EXPORT void orc_math(int which, int n, const float *x, const float *y, float *out) {
-    for (int i = 0; i < n; ++i) {
-        switch (which) {
-        case 0: out[i] = chr_logf(x[i]); break;
-        case 1: out[i] = chr_expf(x[i]); break;
-        case 2: out[i] = chr_sinf(x[i]); break;
-        case 3: out[i] = chr_cosf(x[i]); break;
-        case 4: out[i] = chr_tanf(x[i]); break;
-        case 5: out[i] = chr_asinf(x[i]); break;
-        case 6: out[i] = chr_acosf(x[i]); break;
-        case 7: out[i] = chr_atan2f(y[i], x[i]); break;
-        default: out[i] = 0.0f;
-        }
+/* math probes (tests/test_fmath.py, tests/test_gpu_fmath.py): the result word of one op of
+ * enum chr_fmath_op (chroma_amd.h), as csrc/selftest.hip's fmath_kernel computes it on the device */
+static uint32_t math_bits(int which, float x, float y) {
+    switch (which) {
+    case CHR_FMATH_LOG: return chr_f2u(chr_logf(x));
+    case CHR_FMATH_EXP: return chr_f2u(chr_expf(x));
+    case CHR_FMATH_SIN: return chr_f2u(chr_sinf(x));
+    case CHR_FMATH_COS: return chr_f2u(chr_cosf(x));
+    case CHR_FMATH_TAN: return chr_f2u(chr_tanf(x));
+    case CHR_FMATH_ASIN: return chr_f2u(chr_asinf(x));
+    case CHR_FMATH_ACOS: return chr_f2u(chr_acosf(x));
+    case CHR_FMATH_ATAN2: return chr_f2u(chr_atan2f(y, x));
+    case CHR_FMATH_ATAN: return chr_f2u(chr_atanf(x));
+    case CHR_FMATH_ERF: return chr_f2u(chr_erff(x));
+    case CHR_FMATH_LDEXP: return chr_f2u(chr_ldexpf(x, CHR_FMATH_LDEXP_K(y)));
+    case CHR_FMATH_SAT_U32: return chr_sat_u32(x);
+    case CHR_FMATH_RINT_SMALL: return chr_f2u(chr_rintf_small(x));
+    case CHR_FMATH_SQRT: return chr_f2u(chr_sqrtf(x));
+    case CHR_FMATH_FMA: return chr_f2u(chr_fmaf(x, y, x));
+    case CHR_FMATH_DIV: return chr_f2u(x / y);
+    default: return 0u;
     }
+}
+EXPORT void orc_math_bits(int which, int n, const float *x, const float *y, uint32_t *out) {
+    for (int i = 0; i < n; ++i) out[i] = math_bits(which, x[i], y[i]);
+}
+/* the same as floats (sat_u32: the integer's bits, read them with orc_math_bits) */
+EXPORT void orc_math(int which, int n, const float *x, const float *y, float *out) {
+    for (int i = 0; i < n; ++i) out[i] = chr_u2f(math_bits(which, x[i], y[i]));
 }
 
 /* rayleigh scatter probe: n photons with the given pol/dir, one scatter each from slot 0 */

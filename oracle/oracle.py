@@ -37,6 +37,7 @@ def lib():
         l.orc_propagate_track.argtypes = l.orc_propagate.argtypes + [vp, vp, u64, vp, vp]
         l.orc_fill_state.argtypes = [vp, vp, ctypes.c_int32, ctypes.c_float, vp, vp]
         l.orc_math.argtypes = [i32, i32, vp, vp, vp]
+        l.orc_math_bits.argtypes = [i32, i32, vp, vp, vp]
         l.orc_rayleigh.argtypes = [i32, vp, vp, vp, u32]
         l.orc_render.argtypes = [vp, i32, vp, vp, vp, u32, vp, vp, vp, vp, u32]
         l.orc_transform.argtypes = [i32, vp, i32, ctypes.c_float, vp, vp]
@@ -73,15 +74,26 @@ def uniforms(states, nslots, slot, n):
     return out
 
 
-MATH = {'log': 0, 'exp': 1, 'sin': 2, 'cos': 3, 'tan': 4, 'asin': 5, 'acos': 6, 'atan2': 7}
+# enum chr_fmath_op (chroma_amd.h): atan2 is (y, x) -> chr_atan2f(y, x), hence math('atan2', x, y);
+# ldexp(x, k) takes k in y as a float; fma is fma(x, y, x); div is x / y
+MATH = {'log': 0, 'exp': 1, 'sin': 2, 'cos': 3, 'tan': 4, 'asin': 5, 'acos': 6, 'atan2': 7, 'atan': 8, 'erf': 9,
+        'ldexp': 10, 'sat_u32': 11, 'rint_small': 12, 'sqrt': 13, 'fma': 14, 'div': 15}
+
+
+def math_bits(name, x, y=None):
+    """The result words (uint32) of one op of chroma_fmath.h over x (and y): the
+    float results' bit patterns; for sat_u32 the integers themselves."""
+    x = np.ascontiguousarray(x, dtype=np.float32)
+    y = np.ascontiguousarray(y if y is not None else np.zeros_like(x), dtype=np.float32)
+    assert x.shape == y.shape and x.ndim == 1
+    out = np.zeros(len(x), dtype=np.uint32)
+    lib().orc_math_bits(MATH[name], len(x), _p(x), _p(y), _p(out))
+    return out
 
 
 def math(name, x, y=None):
-    x = np.ascontiguousarray(x, dtype=np.float32)
-    y = np.ascontiguousarray(y if y is not None else np.zeros_like(x), dtype=np.float32)
-    out = np.zeros_like(x)
-    lib().orc_math(MATH[name], len(x), _p(x), _p(y), _p(out))
-    return out
+    bits = math_bits(name, x, y)
+    return bits if name == 'sat_u32' else bits.view(np.float32)
 
 
 def distance_to_mesh(packed, origins, directions):

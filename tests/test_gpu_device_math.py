@@ -88,7 +88,14 @@ def test_rotate():
     _call('chr_selftest_rotate', n, _dev(a.ravel()).gpudata, _dev(t).gpudata, ctypes.c_float(w[0]),
           ctypes.c_float(w[1]), ctypes.c_float(w[2]), out.gpudata)
     want = rotate(a.astype(np.float64), t.astype(np.float64), w.astype(np.float64))
-    assert np.allclose(out.get().reshape(-1, 3), want, atol=1e-5)
+    got = out.get().reshape(-1, 3)
+    assert np.allclose(got, want, atol=1e-5)
+    # and bit for bit with the oracle's rotate (orc_transform restates device_math.h's rotate over the
+    # same chroma_fmath.h; one angle per call) on a 4096-point slice
+    import oracle
+    sl = slice(n // 2, n // 2 + 4096)
+    host = np.concatenate([oracle.transform(p, 1, phi=float(ph), axis=w) for p, ph in zip(a[sl], t[sl])])
+    assert np.array_equal(got[sl].view(np.uint32), host.view(np.uint32))
 
 
 # ---------------------------------------------------------------- test_sample_cdf.py
