@@ -127,6 +127,31 @@ class Channels(object):
         return ids, self.t[self.hit], self.q[self.hit]
 
 
+class Photoelectrons(object):
+    """The photoelectrons of one event, in photon order: channel (int32), t (ns,
+    the smeared time), q_int (uint32 quantised charge) and q = q_int * charge_unit."""
+
+    def __init__(self, channel, t, q_int, q):
+        self.channel, self.t, self.q_int, self.q = channel, t, q_int, q
+
+    def __len__(self):
+        return len(self.channel)
+
+
+class Waveforms(object):
+    """The read-out rows of one event: `channels` (int32, one per row), `trains`
+    (rows x samples uint32 charge words, sample b covering [t_lo + b*dt, t_lo +
+    (b+1)*dt)), `adc` (rows x samples uint16, or None when nothing was
+    digitised) and `outside_q` (uint32 per row: the charge outside the window)."""
+
+    def __init__(self, channels, trains, adc, outside_q, t_lo, dt):
+        self.channels, self.trains, self.adc, self.outside_q = channels, trains, adc, outside_q
+        self.t_lo, self.dt = t_lo, dt
+
+    def __len__(self):
+        return len(self.channels)
+
+
 class Event(object):
     def __init__(self, id=0, vertices=None, photons_beg=None, photons_end=None,
                  photon_tracks=None, photon_parent_trackids=None, hits=None,
@@ -147,3 +172,5 @@ class Event(object):
         self.hits = hits
         self.flat_hits = flat_hits
         self.channels = channels
+        self.photoelectrons = None          # Photoelectrons, and Waveforms: Simulation.simulate(waveforms=spec)
+        self.waveforms = None

@@ -10,5 +10,7 @@ from chroma.gpu.tracks import PhotonTracks  # noqa: F401
 from chroma.gpu.hitmap import GPUHitMap, HostHitMap, HitMap  # noqa: F401
 from chroma.gpu.library import GPUPhotonLibrary, HostPhotonLibrary  # noqa: F401
 from chroma.gpu.daq import GPUDaq, GPUChannels, GPUEventChannels  # noqa: F401
+from chroma.gpu.waveform import (GPUPhotoelectrons, GPUWaveforms, HostWaveforms, WaveformSpec,  # noqa: F401
+                                 waveform_event_groups)
 from chroma.gpu.pdf import GPUPDF, GPUKernelPDF  # noqa: F401
 from chroma.gpu.render import GPURays  # noqa: F401

@@ -176,6 +176,14 @@ _SIGNATURES = {
                                        c_vp, c_vp, c_vp, c_vp, c_vp, c_f32, c_i32, c_i32, c_vp]),
     'chr_daq_acquire_events_many': (c_i32, [ctypes.POINTER(PhotonsDesc), c_i32, c_vp, c_i32, c_vp, c_u32, c_vp, c_u32,
                                             c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_f32, c_i32, c_i32, c_vp]),
+    'chr_daq_acquire_events_pe': (c_i32, [ctypes.POINTER(PhotonsDesc), c_i32, c_vp, c_i32, c_vp, c_u32, c_u32, c_vp,
+                                          c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_f32, c_i32, c_i32, c_vp]),
+    'chr_daq_pe_trains': (c_i32, [c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_vp, c_u32, c_f32, c_f32, c_u32, c_vp, c_vp,
+                                  c_vp, c_vp]),
+    'chr_daq_pe_trains_host': (c_i32, [c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_vp, c_u32, c_f32, c_f32, c_u32, c_vp,
+                                       c_vp, c_vp]),
+    'chr_daq_digitise': (c_i32, [c_vp, c_u32, c_u32, c_vp, c_u32, c_f32, c_f32, c_u32, c_vp, c_vp, c_vp]),
+    'chr_daq_digitise_host': (c_i32, [c_vp, c_u32, c_u32, c_vp, c_u32, c_f32, c_f32, c_u32, c_vp, c_vp]),
     'chr_init_rng_subseq':(c_i32, [c_vp, c_u32, c_u64, c_u64, c_u64, c_vp]),
     'chr_channel_hit_counts': (c_i32, [ctypes.POINTER(PhotonsDesc), c_i32, c_i32, c_u32, c_vp, c_vp, c_vp, c_i32,
                                        c_vp]),

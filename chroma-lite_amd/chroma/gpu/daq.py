@@ -5,8 +5,9 @@ The DAQ turns detected photons into per-channel readout: earliest time
 sample of the charge CDF, quantised by charge_unit) and the OR of the photon
 histories.  Kernels: csrc/daq.hip through the C ABI (chr_daq_begin /
 chr_daq_acquire / chr_daq_end, and chr_daq_acquire_events /
-chr_daq_acquire_events_many for all events of a batch in one call); no host
-fallback.
+chr_daq_acquire_events_many for all events of a batch in one call, and
+chr_daq_acquire_events_pe, which also keeps every accepted photon's time and
+charge for chroma.gpu.waveform); no host fallback.
 """
 import ctypes
 
@@ -190,6 +191,40 @@ class GPUDaq(object):
                      ctypes.byref(self._desc), t_int.gpudata, q_int.gpudata, hist.gpudata, q.gpudata,
                      ctypes.c_float(weight), int(nthreads_per_block), int(max_blocks), current_stream())
         return GPUEventChannels(t_int, q_int, hist, q, nevents, self.nchannels, host=self._event_host_words)
+
+    def acquire_photoelectrons(self, gpuphotons, rng_states, bounds, nthreads_per_block=64, max_blocks=1024,
+                               weight=1.0):
+        """acquire_events that also keeps what it draws (chr_daq_acquire_events_pe):
+        returns (GPUEventChannels, GPUPhotoelectrons).  The channel rows and the
+        rng_states afterwards are bit for bit acquire_events' on the same inputs
+        -- the same stream as acquire_events --; the second value holds, per
+        photon of [bounds[0], bounds[-1]), the channel, time and quantised charge
+        of the photoelectron it made (chroma.gpu.waveform).  The channel rows are
+        views of arrays this GPUDaq reuses, as acquire_events'; the
+        GPUPhotoelectrons owns its arrays."""
+        from chroma.gpu.waveform import GPUPhotoelectrons
+        if self.ndaq != 1:
+            raise ValueError('acquire_photoelectrons runs ndaq = 1 acquisitions only (this GPUDaq has ndaq = %d)'
+                             % self.ndaq)
+        bounds = np.ascontiguousarray(bounds, dtype=np.int64)
+        if bounds.ndim != 1 or len(bounds) < 1:
+            raise ValueError('bounds must be a 1-D array of nevents + 1 photon offsets')
+        nevents = len(bounds) - 1
+        span = int(bounds[-1] - bounds[0])
+        if span < 0:
+            raise ValueError('bounds decrease')
+        t_int, q_int, hist, q = self._event_arrays(nevents * self.nchannels)
+        # one spare word: an empty array has no address to hand over
+        pe = [ga.empty(span + 1, d)[:span] for d in (np.int32, np.float32, np.uint32)]
+        if nevents:
+            ph = gpuphotons._desc()
+            _native.call('chr_daq_acquire_events_pe', ctypes.byref(ph), len(gpuphotons.pos), bounds.ctypes.data,
+                         nevents, rng_states.gpudata, len(rng_states), 0x1 << 2, self.solid_id_map_gpu.gpudata,
+                         ctypes.byref(self._desc), t_int.gpudata, q_int.gpudata, hist.gpudata, q.gpudata,
+                         pe[0].gpudata, pe[1].gpudata, pe[2].gpudata, ctypes.c_float(weight),
+                         int(nthreads_per_block), int(max_blocks), current_stream())
+        chans = GPUEventChannels(t_int, q_int, hist, q, nevents, self.nchannels, host=self._event_host_words)
+        return chans, GPUPhotoelectrons(pe[0], pe[1], pe[2], bounds, self.nchannels, self.charge_unit, t_int.copy())
 
     def acquire_events_many(self, gpuphotons, rng_states, bounds, nthreads_per_block=64, max_blocks=1024, weight=1.0):
         """acquire_events for ndaq > 1 (run_daq_many, daq.py:62-91): begin_acquire

@@ -30,6 +30,7 @@ _TORCH = {np.dtype(np.float32): torch.float32, np.dtype(np.float64): torch.float
           # identical; torch's uint32/uint64 kernels are incomplete)
           np.dtype(np.int32): torch.int32, np.dtype(np.uint32): torch.int32,
           np.dtype(np.int64): torch.int64, np.dtype(np.uint64): torch.int64,
+          np.dtype(np.int16): torch.int16, np.dtype(np.uint16): torch.int16,
           np.dtype(np.uint8): torch.uint8, np.dtype(np.int8): torch.int8, np.dtype(np.bool_): torch.bool}
 
 
@@ -96,7 +97,7 @@ class GPUArray(object):
             raise ValueError('size mismatch: %d vs %d' % (ary.size, self.size))
         base, _ = _base(self.dtype)
         flat = ary.reshape(-1).view(base)
-        if base.kind == 'u' and base.itemsize in (4, 8):
+        if base.kind == 'u' and base.itemsize in (2, 4, 8):
             flat = flat.view(np.dtype('<i%d' % base.itemsize))
         self._t.copy_(torch.from_numpy(flat))
 
@@ -104,7 +105,7 @@ class GPUArray(object):
         if self.dtype.names:
             raise TypeError('fill() on a vector dtype')
         v = value.item() if isinstance(value, np.generic) else value
-        if self.dtype.kind == 'u' and self.dtype.itemsize in (4, 8):
+        if self.dtype.kind == 'u' and self.dtype.itemsize in (2, 4, 8):
             v = int(np.array(v, dtype=self.dtype).view(np.dtype('<i%d' % self.dtype.itemsize)))
         self._t.fill_(v)
         return self

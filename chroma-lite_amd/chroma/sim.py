@@ -6,7 +6,8 @@ max_blocks=1024 -> 524,288 RNG slots) and splits the detected hits back into
 events.  Photon tracking, GPU-resident inputs and the per-event DAQ
 (run_daq=True, chroma.gpu.daq) are supported as in the reference; the DAQ of a
 batch's events runs in groups of one native call each (Simulation.daq_events),
-with the per-event loop's results.
+with the per-event loop's results; simulate(..., waveforms=WaveformSpec(...))
+also fills every event's charge trains and ADC words (chroma.gpu.waveform).
 """
 import os
 import time
@@ -18,6 +19,7 @@ from chroma import event
 from chroma import gpu
 from chroma.gensteps import Gensteps
 from chroma.gpu import gpuarray as ga
+from chroma.gpu.waveform import WaveformSpec, waveform_event_groups  # noqa: F401
 from chroma.itertoolset import peek
 
 
@@ -122,7 +124,8 @@ class Simulation(object):
     daq_events = True
     # bytes of channel rows (16 per channel and event) one group may hold on the
     # device; a cap on device and pinned host memory (a batch of one-photon
-    # events on a large detector would otherwise ask for its product)
+    # events on a large detector would otherwise ask for its product).  With
+    # waveforms the train words count too (WaveformSpec.event_bytes).
     daq_group_bytes = 64 << 20
     # photon_tracking: build ev.photon_tracks, one event.Photons per photon (the
     # reference's list).  False leaves it None for callers who read only
@@ -217,8 +220,22 @@ class Simulation(object):
                                            nthreads_per_block=self.nthreads_per_block,
                                            max_blocks=self.max_blocks).get()
 
+    def _acquire_waveforms(self, b, bounds, spec):
+        """DAQ of the consecutive events [bounds[e], bounds[e+1]) of the batch with
+        their photoelectrons kept (GPUDaq.acquire_photoelectrons: the channels
+        and rng_states of _acquire_events): per event its event.Channels, its
+        event.Waveforms by `spec`, and its event.Photoelectrons or None."""
+        chans, pe = self.gpu_daq.acquire_photoelectrons(b.gpu_photons, self.rng_states, bounds,
+                                                        nthreads_per_block=self.nthreads_per_block,
+                                                        max_blocks=self.max_blocks)
+        wf = pe.trains(spec.trange, spec.nsamples, rows=spec.rows)
+        if spec.template is not None:
+            wf.digitise(spec.template, spec.scale, spec.pedestal, spec.adc_bits)
+        kept = pe.get() if spec.keep_photoelectrons else [None] * len(pe)
+        return chans.get(), wf.get(), kept
+
     def _emit(self, b, keep_photons_beg=False, keep_photons_end=False, keep_hits=True, keep_flat_hits=True,
-              run_daq=False):
+              run_daq=False, waveforms=None):
         """Split a propagated batch back into its events (sim.py:72-110).
 
         With run_daq and daq_events the DAQ runs for a group of events at a time
@@ -226,7 +243,13 @@ class Simulation(object):
         first event is yielded, so its draws fall between the same propagates
         as the per-event loop's.  A caller who abandons the generator inside a
         batch leaves rng_states advanced to the end of the current group, not
-        of the current event."""
+        of the current event.
+
+        With `waveforms` (a WaveformSpec) every group, one of a single event
+        too, runs through _acquire_waveforms, in the groups of
+        waveform_event_groups (the train words count against daq_group_bytes):
+        ev.channels and rng_states are what the run without it gives, and
+        ev.waveforms (ev.photoelectrons) are filled."""
         if keep_photons_end:
             photons_end = self._photons_end(b)
         has_channels = hasattr(self.detector, 'num_channels')
@@ -235,9 +258,11 @@ class Simulation(object):
             batch_hits = self._batch_hits(b)
         run_daq = run_daq and getattr(self, 'gpu_daq', None) is not None
         groups = {}
-        if run_daq and self.daq_events:
+        if run_daq and waveforms is not None:
+            groups = dict(waveform_event_groups(b.bounds, self.gpu_daq.nchannels, self.daq_group_bytes, waveforms))
+        elif run_daq and self.daq_events:
             groups = dict(daq_event_groups(b.bounds, self.gpu_daq.nchannels, self.daq_group_bytes))
-        group_first, group_channels = 0, None
+        group_first, group_channels, group_waveforms = 0, None, None
         flat = None
         if self.photon_tracking and isinstance(b.tracking, gpu.PhotonTracks):
             flat = b.tracking.flat()      # one download of the batch's records, photon-major
@@ -269,7 +294,14 @@ class Simulation(object):
                     ev.hits = {int(ch): ev_hits[ev_hits.channel == ch] for ch in np.unique(ev_hits.channel)}
                 if keep_flat_hits:
                     ev.flat_hits = ev_hits
-            if run_daq:
+            if run_daq and waveforms is not None:
+                if i in groups:
+                    group_first = i
+                    group_waveforms = self._acquire_waveforms(b, b.bounds[i:groups[i] + 1], waveforms)
+                ev.channels, ev.waveforms, ev.photoelectrons = (part[i - group_first] for part in group_waveforms)
+                for part in group_waveforms:
+                    part[i - group_first] = None
+            elif run_daq:
                 if i in groups:
                     group_first, group_channels = i, None
                     if groups[i] - i > 1:           # one event alone is quicker through _acquire (DESIGN)
@@ -328,12 +360,30 @@ class Simulation(object):
         return max(1, int(self.pipeline_batches))
 
     def simulate(self, iterable, keep_photons_beg=False, keep_photons_end=False, keep_hits=True,
-                 keep_flat_hits=True, run_daq=False, max_steps=1000, photons_per_batch=1000000):
+                 keep_flat_hits=True, run_daq=False, max_steps=1000, photons_per_batch=1000000, waveforms=None):
         """sim.py:112-160.  Events are batched as the reference batches them
         (never split, a batch closes once it holds photons_per_batch photons)
         and yielded in order; up to pipeline_batches closed batches are
         propagated in one pipelined call (read ahead from the iterable), with
-        results bit-identical to the reference's one-batch-at-a-time loop."""
+        results bit-identical to the reference's one-batch-at-a-time loop.
+
+        waveforms: a WaveformSpec (with run_daq) also fills ev.waveforms -- the
+        charge trains of the event's photoelectrons per read-out row and, with a
+        template, their ADC words -- and ev.photoelectrons when the spec keeps
+        them.  The DAQ draws what it draws without it (the same stream as
+        acquire_events): ev.channels and rng_states do not change, bit for bit."""
+        if waveforms is not None:
+            if not isinstance(waveforms, WaveformSpec):
+                raise TypeError('waveforms must be a WaveformSpec')
+            if not run_daq:
+                raise ValueError('waveforms need run_daq=True')
+            self._check_waveforms()
+        return self._simulate_events(iterable, keep_photons_beg, keep_photons_end, keep_hits, keep_flat_hits, run_daq,
+                                     max_steps, photons_per_batch, waveforms)
+
+    def _simulate_events(self, iterable, keep_photons_beg, keep_photons_end, keep_hits, keep_flat_hits, run_daq,
+                         max_steps, photons_per_batch, waveforms):
+        """simulate's generator (simulate itself refuses bad arguments when it is called)."""
         if isinstance(iterable, (event.Photons, Gensteps)):
             first, iterable = iterable, [iterable]
         else:
@@ -349,7 +399,7 @@ class Simulation(object):
         elif isinstance(first, event.Vertex):
             raise NotImplementedError('Vertex input not supported in Chroma')
         emit_kw = dict(keep_photons_beg=keep_photons_beg, keep_photons_end=keep_photons_end, keep_hits=keep_hits,
-                       keep_flat_hits=keep_flat_hits, run_daq=run_daq)
+                       keep_flat_hits=keep_flat_hits, run_daq=run_daq, waveforms=waveforms)
         depth = self._pipeline_depth(run_daq)
         stats = [0, 0]
         pending = []
@@ -385,6 +435,10 @@ class Simulation(object):
         if pending:
             yield from flush()
         self.last_pipeline = tuple(stats)
+
+    def _check_waveforms(self):
+        if getattr(self, 'gpu_daq', None) is None:
+            raise ValueError('waveforms need a detector with channels')
 
     def hit_map(self, gensteps, nsources, tbins=0, trange=None, earliest=True, weights=False, max_steps=1000,
                 photons_per_batch=1000000, use_weights=False):
@@ -693,6 +747,10 @@ class ShardedSimulation(Simulation):
         # different streams: generate with Simulation (or chroma.gpu.generate_photons from
         # states seeded alike on every rank) and pass the photons
         raise NotImplementedError('Gensteps input is not sharded: generate the photons first')
+
+    def _check_waveforms(self):
+        # a channel's photoelectrons are spread over the ranks' shares of an event
+        raise NotImplementedError('waveforms are not sharded: use Simulation')
 
     def hit_map(self, *args, **kwargs):
         # the map of a rank's photons would have to be reduced over the ranks (SUM; MIN for tmin)

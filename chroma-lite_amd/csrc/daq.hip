@@ -71,10 +71,11 @@ __global__ __launch_bounds__(BLOCK) void begin_kernel(uint32_t *time_int, uint32
 }
 
 // daq.cu:61-76: the draws for one detected photon on a channel (one uniform, two more
-// when accepted) and the three atomics on that channel's words
-__device__ __forceinline__ void draw_hit(chr_xorwow &rng, const DaqPhotons &ph, uint32_t photon_id, uint32_t history,
+// when accepted) and the three atomics on that channel's words.  True when the photon
+// was accepted, with the photoelectron's time and charge word in pe_time and pe_q.
+__device__ __forceinline__ bool draw_hit(chr_xorwow &rng, const DaqPhotons &ph, uint32_t photon_id, uint32_t history,
                                          const chr_daq_detector &det, float global_weight, uint32_t *time_word,
-                                         uint32_t *q_word, uint32_t *hist_word) {
+                                         uint32_t *q_word, uint32_t *hist_word, float &pe_time, uint32_t &pe_q) {
     const float weight = ph.weights[photon_id] * global_weight;
     if (chr_uniform01(&rng) < weight) {
         const float time = ph.t[photon_id] + sample_cdf_xy(rng, det.time_cdf_len, det.d_time_cdf_x, det.d_time_cdf_y);
@@ -83,7 +84,11 @@ __device__ __forceinline__ void draw_hit(chr_xorwow &rng, const DaqPhotons &ph, 
         atomicMin(time_word, __float_as_uint(time));
         atomicAdd(q_word, charge_int);
         atomicOr(hist_word, history);
+        pe_time = time;
+        pe_q = charge_int;
+        return true;
     }
+    return false;
 }
 
 // daq.cu:35-83 over all chunks of [start, start+n): slot loops over chunk positions
@@ -105,8 +110,10 @@ __global__ __launch_bounds__(BLOCK) void run_daq_kernel(uint32_t *rng_states, ui
         const int channel_index = det.d_solid_id_to_channel_index[solid_id];
         if (!(channel_index >= 0 && (history & detection_state))) continue;
         if (!loaded) { load_rng(rng_states, nslots, slot, rng); loaded = true; }
+        float pe_time;
+        uint32_t pe_q;
         draw_hit(rng, ph, photon_id, history, det, global_weight, time_int + channel_index, q_int + channel_index,
-                 hist + channel_index);
+                 hist + channel_index, pe_time, pe_q);
     }
     if (loaded) store_rng(rng_states, nslots, slot, rng);
 }
@@ -125,6 +132,14 @@ __device__ __forceinline__ int candidate_channel(const DaqPhotons &ph, uint32_t 
     return channel_index;
 }
 
+// The photoelectron records of chr_daq_acquire_events_pe, one per photon of the span
+// [bounds[0], bounds[nevents]) and indexed from its first photon.
+struct PeRecords {
+    int32_t *channel;
+    float *time;
+    uint32_t *q;
+};
+
 // shape (b), pass 1: candidate_channel of photons [first, first+n), one work-item each
 __global__ __launch_bounds__(BLOCK) void candidates_kernel(DaqPhotons ph, uint32_t first, uint32_t n,
                                                            const uint32_t *solid_map, chr_daq_detector det,
@@ -132,6 +147,19 @@ __global__ __launch_bounds__(BLOCK) void candidates_kernel(DaqPhotons ph, uint32
     const uint32_t i = blockIdx.x * BLOCK + threadIdx.x;
     if (i >= n) return;
     cand[i] = candidate_channel(ph, first + i, solid_map, det, detection_state);
+}
+
+// the same pass for the photoelectron variant: every record of the span starts as "no
+// photoelectron" (-1, the 1e9 no-hit time, 0); the draws overwrite those of accepted photons
+__global__ __launch_bounds__(BLOCK) void candidates_pe_kernel(DaqPhotons ph, uint32_t first, uint32_t n,
+                                                              const uint32_t *solid_map, chr_daq_detector det,
+                                                              uint32_t detection_state, int32_t *cand, PeRecords pe) {
+    const uint32_t i = blockIdx.x * BLOCK + threadIdx.x;
+    if (i >= n) return;
+    cand[i] = candidate_channel(ph, first + i, solid_map, det, detection_state);
+    pe.channel[i] = -1;
+    pe.time[i] = 1e9f;
+    pe.q[i] = 0u;
 }
 
 // The draws of run_daq_kernel for events e = 0 .. nevents-1 over photons
@@ -142,15 +170,17 @@ __global__ __launch_bounds__(BLOCK) void candidates_kernel(DaqPhotons ph, uint32
 // (bounds through uniform loads, the wave's first slot in an SGPR).  Only the RNG
 // chain is serial across events: the candidate word of the slot's first position
 // (CAND: read from pass 1's array, shape (b); else computed through last_hit ->
-// solid_map -> channel, shape (a)) is read one event ahead of the draws.
-template <bool CAND>
+// solid_map -> channel, shape (a)) is read one event ahead of the draws.  PE: an accepted
+// photon's record is also written (chr_daq_acquire_events_pe; a photon has one visitor,
+// so plain stores); the walk, the draws and the atomics are the same text.
+template <bool CAND, bool PE>
 __global__ __launch_bounds__(BLOCK) void run_daq_events_kernel(uint32_t *rng_states, uint32_t nslots,
                                                                uint32_t detection_state,
                                                                const uint32_t *__restrict__ bounds, uint32_t nevents,
                                                                uint32_t cap, DaqPhotons ph, const uint32_t *solid_map,
                                                                chr_daq_detector det, const int32_t *__restrict__ cand,
                                                                uint32_t *time_int, uint32_t *q_int, uint32_t *hist,
-                                                               float global_weight) {
+                                                               float global_weight, PeRecords pe) {
     const uint32_t slot = blockIdx.x * BLOCK + threadIdx.x;
     const uint32_t wave_slot = __builtin_amdgcn_readfirstlane(slot);
     const uint32_t first = bounds[0];
@@ -178,7 +208,16 @@ __global__ __launch_bounds__(BLOCK) void run_daq_events_kernel(uint32_t *rng_sta
             if (channel_index < 0) continue;
             if (!loaded) { load_rng(rng_states, nslots, slot, rng); loaded = true; }
             const size_t w = row + (uint32_t)channel_index;
-            draw_hit(rng, ph, b0 + pos, ph.flags[b0 + pos], det, global_weight, time_int + w, q_int + w, hist + w);
+            float pe_time;
+            uint32_t pe_q;
+            const bool accepted = draw_hit(rng, ph, b0 + pos, ph.flags[b0 + pos], det, global_weight, time_int + w,
+                                           q_int + w, hist + w, pe_time, pe_q);
+            if (PE && accepted) {
+                const uint32_t i = b0 + pos - first;
+                pe.channel[i] = channel_index;
+                pe.time[i] = pe_time;
+                pe.q[i] = pe_q;
+            }
         }
     }
     if (loaded) store_rng(rng_states, nslots, slot, rng);
@@ -466,39 +505,42 @@ extern "C" int chr_daq_end(const uint32_t *d_time_int, float *d_time, const uint
     return CHR_OK;
 }
 
-extern "C" int chr_daq_acquire_events(const chr_photons *ph, int32_t nphotons, const int64_t *h_bounds,
-                                      int32_t nevents, uint32_t *d_rng_states, uint32_t rng_nslots,
-                                      uint32_t detection_state, const uint32_t *d_solid_map,
-                                      const chr_daq_detector *det, uint32_t *d_time_int, uint32_t *d_q_int,
-                                      uint32_t *d_history, float *d_q, float global_weight, int32_t ntpb,
-                                      int32_t max_blocks, void *vstream) {
+// chr_daq_acquire_events (pe null) and chr_daq_acquire_events_pe (pe: the three record
+// arrays): one text for the refusals, the walk and the launches
+static int acquire_events(const char *who, const chr_photons *ph, int32_t nphotons, const int64_t *h_bounds,
+                          int32_t nevents, uint32_t *d_rng_states, uint32_t rng_nslots, uint32_t detection_state,
+                          const uint32_t *d_solid_map, const chr_daq_detector *det, uint32_t *d_time_int,
+                          uint32_t *d_q_int, uint32_t *d_history, float *d_q, float global_weight, int32_t ntpb,
+                          int32_t max_blocks, void *vstream, const PeRecords *pe) {
+    if (pe && (!pe->channel || !pe->time || !pe->q))
+        return chr::fail(CHR_ERR_INVALID, "%s: null photoelectron array", who);
     if (!ph || !ph->d_t || !ph->d_flags || !ph->d_last_hit_triangles || !ph->d_weights || !h_bounds ||
         !d_rng_states || !d_solid_map || !det || !det->d_solid_id_to_channel_index || !d_time_int || !d_q_int ||
         !d_history || !d_q)
-        return chr::fail(CHR_ERR_INVALID, "chr_daq_acquire_events: null argument");
+        return chr::fail(CHR_ERR_INVALID, "%s: null argument", who);
     if (!det->d_time_cdf_x || !det->d_time_cdf_y || !det->d_charge_cdf_x || !det->d_charge_cdf_y ||
         det->time_cdf_len < 2 || det->charge_cdf_len < 2)
-        return chr::fail(CHR_ERR_INVALID, "chr_daq_acquire_events: time/charge CDFs missing");
+        return chr::fail(CHR_ERR_INVALID, "%s: time/charge CDFs missing", who);
     if (nevents < 0 || nphotons < 0 || ntpb <= 0 || max_blocks <= 0 || det->nchannels <= 0)
-        return chr::fail(CHR_ERR_INVALID, "chr_daq_acquire_events: bad event count / launch shape / channel count");
+        return chr::fail(CHR_ERR_INVALID, "%s: bad event count / launch shape / channel count", who);
     if (h_bounds[0] < 0 || h_bounds[nevents] > nphotons)
-        return chr::fail(CHR_ERR_INVALID, "chr_daq_acquire_events: bounds [%lld, %lld] outside the %d photons",
+        return chr::fail(CHR_ERR_INVALID, "%s: bounds [%lld, %lld] outside the %d photons", who,
                          (long long)h_bounds[0], (long long)h_bounds[nevents], nphotons);
     int64_t max_n = 0;
     for (int32_t e = 0; e < nevents; ++e) {
         if (h_bounds[e + 1] < h_bounds[e])
-            return chr::fail(CHR_ERR_INVALID, "chr_daq_acquire_events: bounds decrease at event %d", e);
+            return chr::fail(CHR_ERR_INVALID, "%s: bounds decrease at event %d", who, e);
         max_n = std::max(max_n, h_bounds[e + 1] - h_bounds[e]);
     }
     // positions stay below 2^31, so a larger cap visits the same ones (and pos + cap cannot wrap)
     const uint32_t cap = (uint32_t)std::min<uint64_t>((uint64_t)ntpb * max_blocks, 0x80000000u);
     const uint32_t threads = (uint32_t)std::min<int64_t>(cap, max_n);
     if (threads > rng_nslots)
-        return chr::fail(CHR_ERR_INVALID, "chr_daq_acquire_events: %u photons per chunk but only %u rng states",
+        return chr::fail(CHR_ERR_INVALID, "%s: %u photons per chunk but only %u rng states", who,
                          threads, rng_nslots);
     const uint64_t words = (uint64_t)nevents * (uint32_t)det->nchannels;
     if (words > 0x80000000u)
-        return chr::fail(CHR_ERR_INVALID, "chr_daq_acquire_events: %d events of %d channels exceed 2^31 words",
+        return chr::fail(CHR_ERR_INVALID, "%s: %d events of %d channels exceed 2^31 words", who,
                          nevents, det->nchannels);
     if (nevents == 0) return CHR_OK;
 
@@ -507,7 +549,7 @@ extern "C" int chr_daq_acquire_events(const chr_photons *ph, int32_t nphotons, c
                        (uint32_t)words, __builtin_bit_cast(uint32_t, 1e9f));
     CHR_HIP_CHECK(hipGetLastError());
     if (threads > 0) {
-        const bool pass = events_candidate_pass();
+        const bool pass = pe || events_candidate_pass();     // the photoelectron variant is shape (b) always
         const uint32_t first = (uint32_t)h_bounds[0], span = (uint32_t)(h_bounds[nevents] - h_bounds[0]);
         EventBuffers *buf = nullptr;
         CHR_TRY(event_buffers((size_t)nevents + 1, pass ? span : 0, &buf));
@@ -515,18 +557,26 @@ extern "C" int chr_daq_acquire_events(const chr_photons *ph, int32_t nphotons, c
         CHR_HIP_CHECK(hipMemcpyAsync(buf->d_bounds, buf->h_bounds, ((size_t)nevents + 1) * 4, hipMemcpyHostToDevice,
                                      stream));
         DaqPhotons p{ph->d_t, ph->d_weights, ph->d_flags, ph->d_last_hit_triangles};
-        if (pass) {
+        const PeRecords none{nullptr, nullptr, nullptr};
+        if (pe) {
+            hipLaunchKernelGGL(candidates_pe_kernel, dim3(grid_for(span)), dim3(BLOCK), 0, stream, p, first, span,
+                               d_solid_map, *det, detection_state, buf->d_cand, *pe);
+            CHR_HIP_CHECK(hipGetLastError());
+            hipLaunchKernelGGL((run_daq_events_kernel<true, true>), dim3(grid_for(threads)), dim3(BLOCK), 0, stream,
+                               d_rng_states, rng_nslots, detection_state, buf->d_bounds, (uint32_t)nevents, cap, p,
+                               d_solid_map, *det, buf->d_cand, d_time_int, d_q_int, d_history, global_weight, *pe);
+        } else if (pass) {
             hipLaunchKernelGGL(candidates_kernel, dim3(grid_for(span)), dim3(BLOCK), 0, stream, p, first, span,
                                d_solid_map, *det, detection_state, buf->d_cand);
             CHR_HIP_CHECK(hipGetLastError());
-            hipLaunchKernelGGL(run_daq_events_kernel<true>, dim3(grid_for(threads)), dim3(BLOCK), 0, stream,
+            hipLaunchKernelGGL((run_daq_events_kernel<true, false>), dim3(grid_for(threads)), dim3(BLOCK), 0, stream,
                                d_rng_states, rng_nslots, detection_state, buf->d_bounds, (uint32_t)nevents, cap, p,
-                               d_solid_map, *det, buf->d_cand, d_time_int, d_q_int, d_history, global_weight);
+                               d_solid_map, *det, buf->d_cand, d_time_int, d_q_int, d_history, global_weight, none);
         } else {
-            hipLaunchKernelGGL(run_daq_events_kernel<false>, dim3(grid_for(threads)), dim3(BLOCK), 0, stream,
+            hipLaunchKernelGGL((run_daq_events_kernel<false, false>), dim3(grid_for(threads)), dim3(BLOCK), 0, stream,
                                d_rng_states, rng_nslots, detection_state, buf->d_bounds, (uint32_t)nevents, cap, p,
                                d_solid_map, *det, (const int32_t *)nullptr, d_time_int, d_q_int, d_history,
-                               global_weight);
+                               global_weight, none);
         }
         CHR_HIP_CHECK(hipGetLastError());
     }
@@ -536,6 +586,30 @@ extern "C" int chr_daq_acquire_events(const chr_photons *ph, int32_t nphotons, c
     // the pinned bounds are rewritten by the next call, and GPUDaq.acquire synchronises too (daq.py:91)
     CHR_HIP_CHECK(hipStreamSynchronize(stream));
     return CHR_OK;
+}
+
+extern "C" int chr_daq_acquire_events(const chr_photons *ph, int32_t nphotons, const int64_t *h_bounds,
+                                      int32_t nevents, uint32_t *d_rng_states, uint32_t rng_nslots,
+                                      uint32_t detection_state, const uint32_t *d_solid_map,
+                                      const chr_daq_detector *det, uint32_t *d_time_int, uint32_t *d_q_int,
+                                      uint32_t *d_history, float *d_q, float global_weight, int32_t ntpb,
+                                      int32_t max_blocks, void *stream) {
+    return acquire_events("chr_daq_acquire_events", ph, nphotons, h_bounds, nevents, d_rng_states, rng_nslots,
+                          detection_state, d_solid_map, det, d_time_int, d_q_int, d_history, d_q, global_weight, ntpb,
+                          max_blocks, stream, nullptr);
+}
+
+extern "C" int chr_daq_acquire_events_pe(const chr_photons *ph, int32_t nphotons, const int64_t *h_bounds,
+                                         int32_t nevents, uint32_t *d_rng_states, uint32_t rng_nslots,
+                                         uint32_t detection_state, const uint32_t *d_solid_map,
+                                         const chr_daq_detector *det, uint32_t *d_time_int, uint32_t *d_q_int,
+                                         uint32_t *d_history, float *d_q, int32_t *d_pe_channel, float *d_pe_time,
+                                         uint32_t *d_pe_q, float global_weight, int32_t ntpb, int32_t max_blocks,
+                                         void *stream) {
+    const PeRecords pe{d_pe_channel, d_pe_time, d_pe_q};
+    return acquire_events("chr_daq_acquire_events_pe", ph, nphotons, h_bounds, nevents, d_rng_states, rng_nslots,
+                          detection_state, d_solid_map, det, d_time_int, d_q_int, d_history, d_q, global_weight, ntpb,
+                          max_blocks, stream, &pe);
 }
 
 extern "C" int chr_daq_acquire_events_many(const chr_photons *ph, int32_t nphotons, const int64_t *h_bounds,

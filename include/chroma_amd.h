@@ -598,6 +598,31 @@ int chr_daq_acquire_events_many(const chr_photons *ph, int32_t nphotons, const i
                                 int32_t ndaq, float global_weight, int32_t nthreads_per_block, int32_t max_blocks,
                                 void *stream);
 
+/* chr_daq_acquire_events that also keeps what it draws: one photoelectron
+ * record per photon of the span [h_bounds[0], h_bounds[nevents]), indexed from
+ * the span's first photon (record i belongs to photon h_bounds[0] + i), in three
+ * device arrays of that many entries.  Every record is written: a photon the DAQ
+ * accepts (selected as a candidate, its uniform below weight * global_weight)
+ * gets its channel in d_pe_channel, the float time handed to the earliest-time
+ * minimum in d_pe_time and its quantised charge word in d_pe_q; every other
+ * photon gets -1, the 1e9 no-hit time and 0.  A photon makes at most one
+ * photoelectron, so the records need no atomics and come in photon order.  The
+ * channel rows, d_q and the RNG slot states afterwards are bit-identical to
+ * chr_daq_acquire_events on the same inputs: the same slots, chunks and events
+ * walked, the same draws in the same order -- the same stream.  Folding the
+ * records per (event, channel) gives the rows back: unsigned minimum of the
+ * times' bit patterns, sum of the charge words mod 2^32 (the history is the OR
+ * of the accepted photons' flags).  The candidate pass always runs
+ * (CHR_DAQ_EVENTS_SHAPE applies to chr_daq_acquire_events only).  Refusals as
+ * chr_daq_acquire_events, and a null record array; all before any launch.
+ * Synchronous. */
+int chr_daq_acquire_events_pe(const chr_photons *ph, int32_t nphotons, const int64_t *h_bounds, int32_t nevents,
+                              uint32_t *d_rng_states, uint32_t rng_nslots, uint32_t detection_state,
+                              const uint32_t *d_solid_map, const chr_daq_detector *det,
+                              uint32_t *d_time_int, uint32_t *d_q_int, uint32_t *d_history, float *d_q,
+                              int32_t *d_pe_channel, float *d_pe_time, uint32_t *d_pe_q,
+                              float global_weight, int32_t nthreads_per_block, int32_t max_blocks, void *stream);
+
 /* Detected photons per channel, ACCUMULATED into d_counts[nchannels] (u32; the
  * caller zeroes it): the selection of count_photon_hits (propagate.cu:172-199)
  * histogrammed by channel.  No reference counterpart -- it is the per-rank
@@ -692,6 +717,85 @@ int chr_hitmap_last_path(void);
 int chr_hitmap_accumulate_host(const chr_photons *ph, int32_t start_photon, int32_t nphotons,
                                uint32_t detection_state, const uint32_t *h_solid_map,
                                const int32_t *h_solid_id_to_channel_index, const chr_hitmap_desc *desc);
+
+/* ---------------------------------------------------------------- waveforms
+ * The pulse train behind a channel's one time and one charge: the photoelectron
+ * records of chr_daq_acquire_events_pe binned into charge trains per (event,
+ * channel) row, and the trains convolved with a single-photoelectron template
+ * and quantised to ADC words.  No reference counterpart: the reference's DAQ
+ * keeps the earliest time and the summed charge only.  Nothing here draws a
+ * random number (electronic noise would need draws and a stream contract of its
+ * own: it is not modelled).
+ *
+ * Trains.  The window is (t_lo, inv, nsamples) with inv = nsamples / (t_hi -
+ * t_lo) computed once by the caller in float32, as a hit map's.  Arrays (device
+ * for chr_daq_pe_trains, host for chr_daq_pe_trains_host):
+ *   pe_channel, pe_time, pe_q   the records, h_bounds[nevents] - h_bounds[0] each
+ *   row_of_word[nevents*nchannels]  i32, optional (NULL: every word has its row)
+ *   trains[nrows*nsamples]      u32, at most 2^31 words
+ *   outside_q[nrows]            u32
+ *   dropped                     one u32 word
+ * The call first zeroes trains, outside_q and dropped.  Then, for record i of
+ * the span, in this order (csrc/waveform.h, one text for the device and the
+ * host twin):
+ *   1. c = pe_channel[i]; c < 0: no photoelectron, stop.  c >= nchannels:
+ *      dropped += 1, stop.
+ *   2. e = the event of photon h_bounds[0] + i: h_bounds[e] <= it < h_bounds[e+1].
+ *   3. w = e*nchannels + c; row = row_of_word[w], or w without a map (nrows must
+ *      then be nevents*nchannels).  row < 0 or row >= nrows: dropped += 1, stop.
+ *   4. the time bin of the hit map's rule step 6 (csrc/hitmap.h, the same
+ *      function): x = (pe_time[i] - t_lo) * inv, one float32 subtract and one
+ *      float32 multiply, never contracted; x >= 0.0f && x < (float)nsamples:
+ *      trains[row*nsamples + (uint32_t)x] += pe_q[i].  A time exactly t_lo is
+ *      in bin 0.
+ *   5. otherwise (before the window, at or after its upper edge, infinite or
+ *      NaN): outside_q[row] += pe_q[i].
+ * Every update is an integer add mod 2^32, so the words are a function of the
+ * records alone, whatever the order, and for every row that the map gives
+ * exactly the records of one (event, channel)
+ *   sum_b trains[row][b] + outside_q[row] == q_int[event][channel]  (mod 2^32)
+ * with q_int the charge word chr_daq_acquire_events_pe left for it.
+ * CHR_ERR_INVALID before anything is read or launched for: a null required
+ * pointer; nevents < 0 or nchannels <= 0; nsamples == 0; t_lo or inv not
+ * finite, inv <= 0; nevents*nchannels or nrows*nsamples above 2^31; bounds
+ * negative, decreasing or beyond 2^31; no map and nrows != nevents*nchannels.
+ * Synchronous. */
+int chr_daq_pe_trains(const int32_t *d_pe_channel, const float *d_pe_time, const uint32_t *d_pe_q,
+                      const int64_t *h_bounds, int32_t nevents, int32_t nchannels, const int32_t *d_row_of_word,
+                      uint32_t nrows, float t_lo, float inv, uint32_t nsamples, uint32_t *d_trains,
+                      uint32_t *d_outside_q, uint32_t *d_dropped, void *stream);
+/* The same on the host (no GPU needed): every pointer addresses HOST memory.
+ * Word-identical to chr_daq_pe_trains, with the same refusals. */
+int chr_daq_pe_trains_host(const int32_t *h_pe_channel, const float *h_pe_time, const uint32_t *h_pe_q,
+                           const int64_t *h_bounds, int32_t nevents, int32_t nchannels, const int32_t *h_row_of_word,
+                           uint32_t nrows, float t_lo, float inv, uint32_t nsamples, uint32_t *h_trains,
+                           uint32_t *h_outside_q, uint32_t *h_dropped);
+
+/* words of LDS one row may take in chr_daq_digitise: nsamples + min(ntaps, nsamples) (64 KB) */
+#define CHR_WAVE_LDS_WORDS 16384
+
+/* Digitiser.  adc[nrows*nsamples] (u16) from trains[nrows*nsamples], a
+ * single-photoelectron template of ntaps floats, scale (the caller's charge
+ * unit times gain, folded into one float), pedestal and adc_max <= 65535.  The
+ * call first zeroes the one-word `bad`.  Then, for sample s of a row
+ * (csrc/waveform.h, one text for both sides):
+ *   1. a row whose train is all zero: v = 0 for every sample, without step 2-3.
+ *   2. v = 0; for k = 0 .. min(ntaps - 1, s), ascending:
+ *   3.     v = fmaf(template[k], (float)trains[row][s - k], v), single-rounded.
+ *   4. x = fmaf(v, scale, pedestal); x NaN: adc = 0 and bad += 1.
+ *   5. otherwise adc = min(sat_u32(x + 0.5f), adc_max), sat_u32 the saturating
+ *      conversion of the DAQ's charge words (negatives give 0).
+ * Rows are independent.  CHR_ERR_INVALID before anything is read or launched
+ * for: a null pointer; nsamples == 0 or ntaps == 0; nrows*nsamples above 2^31;
+ * nsamples + min(ntaps, nsamples) above CHR_WAVE_LDS_WORDS; adc_max > 65535.
+ * Async on `stream`. */
+int chr_daq_digitise(const uint32_t *d_trains, uint32_t nrows, uint32_t nsamples, const float *d_template,
+                     uint32_t ntaps, float scale, float pedestal, uint32_t adc_max, uint16_t *d_adc, uint32_t *d_bad,
+                     void *stream);
+/* The same on the host (no GPU needed), word-identical, with the same refusals. */
+int chr_daq_digitise_host(const uint32_t *h_trains, uint32_t nrows, uint32_t nsamples, const float *h_template,
+                          uint32_t ntaps, float scale, float pedestal, uint32_t adc_max, uint16_t *h_adc,
+                          uint32_t *h_bad);
 
 /* --------------------------------------------------------- photon library
  * The consumer of a hit map: from the map of a set of sources (the library,
